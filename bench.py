@@ -6,18 +6,23 @@ Unet3D_with_Conv3D dim=64 (1,2,4), state (B,32,7,64,64), B=64 per GPU, 1000-step
 conformal quantile on (Q comes from the HIP conformal-score kernel on a calibration shard + all-gather + rank select and
 feeds the guidance).  At N GPUs the batch axis is sharded, 64 trajectories per GPU (N=8 is BASELINE configs[4], "C5":
 B=512, calibration n=8x25, alpha=0.04).  `--workload c2` (1D Burgers Unet2D dim 64, B=256) and `--workload c3` (tokamak
-Unet1D dim 256, B=128) run the other single-GPU configs through the same harness; at N=1 a few steps of each are also
-reported under `extra`.
+Unet1D dim 256, B=128) run the other single-GPU configs through the same harness; with `--full` at N=1 a few steps of each
+are also reported under `extra`.
 
 A "step" is ONE denoising step of the whole batch: U-Net epsilon prediction + guidance reduction + fused posterior
 update + step counter, replayed from one captured hipGraph.  A trajectory costs exactly `timesteps`=1000 such steps, so
 value = global_batch / (1000 * seconds_per_step).
 
+A plain run sets up (weights, conditions, the conformal quantile), warms up, times `--steps` steps and prints the headline;
+`--dump-outputs DIR` also writes the state the last timed step left (`dump_outputs`).  Everything else -- `roofline`,
+`cpu_baseline`, the `extra` workloads and checks, the side file -- runs only with `--full` (which `--all-extras`,
+`--other-precisions`, `--cpu-all-cores`, `--full-sample`, `--full-calibration` and `--cpu-c1-full` imply).
+
 `python bench.py --gpus N` with N > 1 launches itself: the parent touches no GPU and starts N fresh worker processes
 through `python -m torch.distributed.run` (one rank per GPU, RCCL); under an external torch.distributed.run (WORLD_SIZE
 set) it is a worker directly.  Rank 0 prints the one JSON line.
 
-`roofline`: the dominant kernel (the fp32-MFMA Winograd conv), HIP events on the launch stream.  `achieved` / `frac` are
+`roofline` (--full): the dominant kernel (the fp32-MFMA Winograd conv), HIP events on the launch stream.  `achieved` / `frac` are
 the MFMA FLOPs the kernel actually issues / second against the 157.3 TFLOP/s fp32 matrix peak (never above 1);
 `effective_tflops` is the direct-form (algorithmic) rate the same launch stands for.  `roofline.stages` carries the
 stage fractions the north star names: GroupNorm-apply GB/s against 8 TB/s, the Conv3d+GN+SiLU block as a whole, and the
@@ -55,6 +60,7 @@ T_DDPM = 1000
 DEFAULT_B = {"c2": 256, "c3": 128, "c4": 64}
 HEADLINE_MAX_BYTES = 6144                 # the last stdout line stays a headline the driver parses
 PMC_FILES = ("r6_pmc_traffic.json",)      # stamped with the kernel-source hash they were collected on (tools/pmc_to_json.py)
+DUMP_MAX_ELEMENTS = 8 << 20               # --dump-outputs: 32 MB of float32 over all ranks (the C4 state alone is 235 MB)
 
 
 # --------------------------------------------------------------------------- launcher (N > 1 without a torchrun parent)
@@ -469,6 +475,22 @@ def build_roofline(S, lib, stream, step_ms, wl):
     return roof
 
 
+def dump_outputs(out_dir, x, rank, world):
+    """--dump-outputs: the sampler state after the last timed step (what a caller of the sampler receives) as float32
+    `state.npy` (`state_rank<r>.npy` at N > 1).  A state larger than its share of DUMP_MAX_ELEMENTS is written as a fixed sample:
+    the elements at indices drawn from a CPU generator seeded 0, sorted -- the same ones on every run of the same shape."""
+    import numpy as np
+    import torch
+    flat = x.detach().reshape(-1)
+    n = DUMP_MAX_ELEMENTS // world
+    if flat.numel() > n:
+        idx = torch.randint(flat.numel(), (n,), generator=torch.Generator().manual_seed(0)).sort().values
+        flat = flat[idx.to(flat.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    name = "state" if world == 1 else f"state_rank{rank}"
+    np.save(os.path.join(out_dir, name + ".npy"), flat.float().cpu().numpy())
+
+
 def selftest_worker(a):
     """`--selftest-launcher`: the launcher / rendezvous / relay path without a GPU (CPU tests, gloo): every rank contributes
     a shard of synthetic conformal (score, weight) pairs, the all-gather + quantile epilogue runs, the max-over-ranks timer is
@@ -578,11 +600,13 @@ def worker(a):
             clocks["sclk_mhz_before"], clocks["power_w_before"] = round(idle[0]), round(idle[1])
         finite = bool(torch.isfinite(S.x).all().item())
         step_ms = dt / a.steps * 1e3
-        roof = build_roofline(S, lib, side.cuda_stream, step_ms, wl) if rank == 0 else None
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, S.x, rank, world)
+        roof = build_roofline(S, lib, side.cuda_stream, step_ms, wl) if rank == 0 and a.full else None
         S.close()
         t_head = time.perf_counter() - t_start
 
-        if world == 1 and not a.no_extra:
+        if a.full and world == 1 and not a.no_extra:
             import bench_extras as bx
             ctx = types.SimpleNamespace(workload=workload, timed=timed, rank=rank, world=world, step_seconds=_oracle_step_seconds,
                                         build_roofline=lambda S_, ms_, wl_: build_roofline(S_, lib, side.cuda_stream, ms_, wl_))
@@ -606,7 +630,7 @@ def worker(a):
     if rank == 0:
         cf = W["conformal"]
         cpu = None
-        if not a.no_cpu_baseline and world == 1:              # reported on rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:   # reported on rank 0 at N=1 only
             t0 = time.perf_counter()
             cb = a.cpu_batch or {"c2": 32, "c3": 32, "c4": 1}[wl]
             cpu = cpu_baseline(wl, cb, a.cpu_steps or (3 if wl != "c4" else 2), a.dim, all_cores=a.cpu_all_cores)
@@ -615,17 +639,20 @@ def worker(a):
             import bench_extras as bx
             extra["cpu_c1_full"] = bx.cpu_c1_full(cpu_model)
         extra.setdefault("phases_s", {}).update(setup=round(t_setup, 2), headline=round(t_head - t_setup, 2))
-        # the report: every stage, every kernel, every extra workload -> the side file; the line below stays a headline
-        report = {"roofline_all_kernels": roof.pop("all_kernels"), "roofline_notes": roof.pop("notes"),
-                  "conformal": dict(cf, Q=round(cf["Q"], 6)), "gpu_sensors": clocks, "cpu_baseline": cpu, "extra": extra}
         extra_file = None
-        try:
-            with open(a.extra_file, "w") as fh:
-                json.dump(report, fh, indent=1)
-            extra_file = os.path.relpath(a.extra_file, ROOT) if os.path.abspath(a.extra_file).startswith(ROOT) else a.extra_file
-        except OSError as e:                                  # read-only tree: the headline still prints
-            print(f"bench.py: could not write {a.extra_file}: {e}", file=sys.stderr)
-        print(f"bench.py: report -> {a.extra_file}; phases (s): {extra.get('phases_s')}", file=sys.stderr, flush=True)
+        if a.full:
+            # the report: every stage, every kernel, every extra workload -> the side file; the line below stays a headline
+            report = {"roofline_all_kernels": roof.pop("all_kernels"), "roofline_notes": roof.pop("notes"),
+                      "conformal": dict(cf, Q=round(cf["Q"], 6)), "gpu_sensors": clocks, "cpu_baseline": cpu, "extra": extra}
+            try:
+                with open(a.extra_file, "w") as fh:
+                    json.dump(report, fh, indent=1)
+                extra_file = os.path.relpath(a.extra_file, ROOT) if os.path.abspath(a.extra_file).startswith(ROOT) else a.extra_file
+            except OSError as e:                              # read-only tree: the headline still prints
+                print(f"bench.py: could not write {a.extra_file}: {e}", file=sys.stderr)
+            print(f"bench.py: report -> {a.extra_file}; phases (s): {extra.get('phases_s')}", file=sys.stderr, flush=True)
+        else:
+            print(f"bench.py: phases (s): {extra['phases_s']}", file=sys.stderr, flush=True)
         print(json.dumps(headline(a, world, B, value, step_ms, W, roof, cpu, clocks, cf, backend, ranks_seen, extra, extra_file)),
               flush=True)
     if world > 1:
@@ -643,8 +670,9 @@ def headline(a, world, B, value, step_ms, W, roof, cpu, clocks, cf, backend, ran
         "config": {"workload": W["desc"], "batch_per_gpu": B, "global_batch": world * B, "ddpm_timesteps": T_DDPM,
                    "step": "U-Net + guidance + posterior update of the whole batch, one hipGraph replay",
                    "parallelism": f"batch-sharded x{world}, no data-path collective", "conv_precision": a.precision},
-        "roofline": roof,
     }
+    if roof:
+        out["roofline"] = roof
     if cpu:
         out["cpu_baseline"] = {k: cpu[k] for k in ("value", "unit", "cores", "kind", "sample", "cpu_model")}
     out["conformal"] = {"Q": round(cf["Q"], 6), "n_cal": cf["n_cal"], "alpha": cf["alpha"],
@@ -664,9 +692,10 @@ def headline(a, world, B, value, step_ms, W, roof, cpu, clocks, cf, backend, ran
     out["extra_file"] = extra_file
     line = json.dumps(out)
     if len(line) > HEADLINE_MAX_BYTES:                        # never print a line the driver cannot parse: shed the optional keys
-        sheds = [lambda: out.pop("extra", None), lambda: out.pop("gpu_sensors", None), lambda: out.pop("conformal", None),
-                 lambda: roof.pop("top_kernels", None),
-                 lambda: roof.update(stages={k: v.get("frac") for k, v in list(roof["stages"].items())[:16]})]
+        sheds = [lambda: out.pop("extra", None), lambda: out.pop("gpu_sensors", None), lambda: out.pop("conformal", None)]
+        if roof:
+            sheds += [lambda: roof.pop("top_kernels", None),
+                      lambda: roof.update(stages={k: v.get("frac") for k, v in list(roof["stages"].items())[:16]})]
         for shed in sheds:
             shed()
             if len(json.dumps(out)) <= HEADLINE_MAX_BYTES:
@@ -677,8 +706,12 @@ def headline(a, world, B, value, step_ms, W, roof, cpu, clocks, cf, backend, ran
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the CPU baseline, the extra workloads and checks, and the side file (--extra-file)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step to DIR/state.npy (float32; a fixed sample if large)")
     ap.add_argument("--workload", default="c4", choices=["c2", "c3", "c4", "c5"],
                     help="c4 (default) = the north-star configuration, 2D smoke B=64 per GPU; c5 = the same, named for N=8")
     ap.add_argument("--batch", type=int, default=0, help="trajectories per GPU (default: 256 / 128 / 64 for c2 / c3 / c4)")
@@ -687,7 +720,7 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp32-wino2d", "fp32-wino1d", "fp32-direct"],
                     help="conv arithmetic: fp32 MFMA with Winograd F(2x2x2,3x3x3) / F(2x2,3x3) / F(2,3) on the 3-tap convs (default), "
                          "without the depth transform, F(2,3) along W only, or the fp32 direct form everywhere")
-    ap.add_argument("--no-extra", action="store_true", help="skip the calibration sample and the other workloads at N=1")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the calibration sample and the other workloads at N=1")
     ap.add_argument("--extra-workloads", default="c2,c3",
                     help="other configs timed at N=1 and written to the side file (keys of bench_extras.EXTRA_WORKLOADS)")
     ap.add_argument("--all-extras", action="store_true",
@@ -695,7 +728,7 @@ def main():
                          "comparison of the fine-tuning step, the 1-D fine-tuning steps, the smoke score check "
                          "(tools/collect_profiles.sh passes it; minutes)")
     ap.add_argument("--extra-file", default=os.path.join(ROOT, "bench_extra.json"),
-                    help="side file for everything that is not the headline (named in the headline as `extra_file`)")
+                    help="--full: side file for everything that is not the headline (named in the headline as `extra_file`)")
     ap.add_argument("--cpu-all-cores", action="store_true", help="cpu_baseline: also one step with a thread per physical core")
     ap.add_argument("--split-small", action="store_true", help="the headline workload's net with split_small_grids (small-batch plan)")
     ap.add_argument("--extra-steps", type=int, default=20)
@@ -713,6 +746,9 @@ def main():
     ap.add_argument("--cpu-batch", type=int, default=0)
     ap.add_argument("--cpu-steps", type=int, default=0)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    a.full = a.full or any((a.all_extras, a.other_precisions, a.cpu_all_cores, a.full_sample, a.full_calibration, a.cpu_c1_full))
     if a.all_extras:
         import bench_extras as bx
         a.extra_workloads = bx.ALL_EXTRA_WORKLOADS

@@ -81,3 +81,36 @@ def test_bench_defaults_are_the_short_run():
     assert '"--cpu-all-cores", action="store_true"' in src and '"--all-extras", action="store_true"' in src
     import bench_extras as bx
     assert set(bx.ALL_EXTRA_WORKLOADS.split(",")) <= set(bx.EXTRA_WORKLOADS)
+
+
+def test_headline_of_a_plain_run():
+    """without --full there is no roofline, CPU baseline, extra or side file; the contract keys stay"""
+    import bench
+    a, W, roof, cpu, clocks, cf, extra = _fake_inputs(0)
+    out = bench.headline(a, 1, 64, 0.2742, 233.4, W, None, None, clocks, cf, None, 1, {"phases_s": {"setup": 6.0}}, None)
+    back = json.loads(json.dumps(out))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in back, k
+    assert back["ms_per_step"] == 233.4 and back["steps"] == 20 and back["extra_file"] is None
+    assert not {"roofline", "cpu_baseline", "extra"} & set(back)
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a small state is written whole; a large one as the same seeded sample of its elements on every run,
+    split over the ranks within the same budget"""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMENTS", 1000)
+    small = torch.randn(2, 3, 50)
+    bench.dump_outputs(str(tmp_path / "s"), small, 0, 1)
+    got = np.load(tmp_path / "s" / "state.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.reshape(-1).numpy())
+    big = torch.arange(64 * 7 * 64, dtype=torch.float32).reshape(64, 7, 64)
+    bench.dump_outputs(str(tmp_path / "a"), big, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), big.clone(), 0, 1)
+    a, b = np.load(tmp_path / "a" / "state.npy"), np.load(tmp_path / "b" / "state.npy")
+    assert a.shape == (1000,) and np.array_equal(a, b)
+    assert (np.diff(a) >= 0).all() and a.min() >= 0 and a.max() < big.numel()        # sorted elements of the state
+    bench.dump_outputs(str(tmp_path / "r"), big, 1, 2)
+    assert np.load(tmp_path / "r" / "state_rank1.npy").shape == (500,)

@@ -64,6 +64,8 @@ def _worker_c5(rank, world, port, q):
     import torch.distributed as dist
     from safediffcon_amd import conformal
     from safediffcon_amd.dist import init_from_env, shard, shard_range
+    # the CPU path even where a GPU is visible: init_from_env would bind rank r to cuda:r, and one GPU has no cuda:1..7
+    torch.cuda.is_available = lambda: False
     r, w, local = init_from_env("gloo")
     assert (r, w, local) == (rank, world, rank) and dist.get_world_size() == world
     g = torch.Generator().manual_seed(11)

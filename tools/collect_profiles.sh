@@ -11,8 +11,8 @@ python3 tools/pmc_to_json.py $O/pmc_fetch $O/pmc_write $O/pmc_sq $O/pmc_cases.js
 cp $O/r6_pmc_traffic.json $O/r6_pmc_mfma_busy.json profiles/
 find $O -name "*kernel_trace.csv" -delete
 echo "pmc done"
-# the default run (what the driver runs: one compact headline on stdout, the report in the side file), then every extra
-( time timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --extra-file $O/r6_bench_c4_extra.json > $O/r6_bench_c4.json.log 2> $O/bench_c4.err ) 2> $O/bench_c4.time || exit 1
+# the full run (one compact headline on stdout, the report in the side file), then every extra
+( time timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full --extra-file $O/r6_bench_c4_extra.json > $O/r6_bench_c4.json.log 2> $O/bench_c4.err ) 2> $O/bench_c4.time || exit 1
 echo "bench c4 done"; wc -c $O/r6_bench_c4.json.log; tail -3 $O/bench_c4.time
 timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --all-extras --extra-file $O/r6_bench_c4_all_extras_extra.json > $O/r6_bench_c4_all_extras.json.log 2> $O/bench_c4_all.err || exit 13
 echo "bench c4 --all-extras done"

@@ -71,8 +71,8 @@ typedef struct SdcConvDesc {
     int32_t pD, pH, pW;          /* padding, in the (virtually upsampled) input space */
     int32_t uD, uH, uW;          /* virtual input upsample factor, 1 or 2 */
     int32_t up_mode;             /* 0 nearest, 1 zero-insert */
-    int32_t precision;           /* conv algorithm and layout of the wp buffer (0, 2, 3 and 4 are fp32 end to end and differ by
-                                    rounding order only; the drop-in nets use 4):
+    int32_t precision;           /* conv algorithm and layout of the wp buffer (0, 2, 3, 4 and 5 are fp32 end to end and differ by
+                                    rounding order only; the drop-in nets use 4; 6 and 7 round the 3-tap convs' operands to fp16):
                                     0 = fp32 MFMA, direct implicit GEMM everywhere (k-ordered fp32 FMA chains); wp = Wp
                                     2 = fp32 MFMA, Winograd F(2,3) along W on the 3-wide stride-1 convs (2/3 of the matrix
                                         work); wp = Wp followed, when kW == 3, by the transformed taps
@@ -95,7 +95,25 @@ typedef struct SdcConvDesc {
                                         (1/24,1/12,1/6), (1/24,-1/12,1/6), (0,0,1)).  Opt-in, not the nets' default: on MI355X it is
                                         no faster than 2's kernel (the transform is not hidden behind the MFMAs it saves) and
                                         rounds three times coarser (~3e-6 of the output scale).
-                                    (1 was a split-bf16 mode in rounds 1-2; removed: every mode is fp32 arithmetic) */
+                                    6 = as 4, plus fp16 operands with fp32 accumulation (conv_f16_kernel, v_mfma_f32_32x32x16_f16:
+                                        activations rounded to fp16 RNE as they are staged, fp32 in HBM) for the 1x1x3 / 1x3x3 /
+                                        3x3x3 stride-1 pad-1 convs over rows of 16 / 32 / 64 / 128 columns that its measured dispatch
+                                        table lists (csrc/sdc_conv_f16.hip f16_faster, DESIGN.md section 11: every 3x3x3 conv, the 3x3
+                                        convs over rows of 64 / 16 and of 32 from 32768 outputs per sample, the 1x3 convs from 32768
+                                        outputs per sample; keyed on per-sample sizes, so a sample's bits do not depend on its batch).
+                                        Opt-in, samplers only.  For those tap shapes the buffer is 4's buffer, zero-padded to a multiple
+                                        of 4 floats (16 bytes), followed by Wh[tap][ci / 32][co][ci % 32] = (fp16, RNE) w[co][ci][tap],
+                                        Cin zero-padded to whole chunks of 32 (taps * ceil(Cin / 32) * 32 * Cout / 2 floats: +8 % on a
+                                        3x3x3 buffer, +12 % on a 3x3 one, +21 % on a 1x3 one, stored for every such conv, including those
+                                        the table leaves on 4's kernels); other tap shapes: layout of 4.  Every other conv, and
+                                        sdc_conv_splitk, runs 4's kernels on the buffer's precision-4 prefix.  The GroupNorm sums of
+                                        sdc_conv_gn are fused where S % 256 == 0 or whole samples of 64 / 128 positions share a tile.
+                                    7 = test and measurement hook, not a user mode: 6 without the dispatch table (every conv the fp16
+                                        kernel covers), the same buffer.
+                                    Rounding of 6 / 7: fp16 x fp16 products are exact in fp32, so the result is an fp64 conv of the
+                                    rounded operands up to fp32 summation order (~2e-4 of the output rms from the operand rounding;
+                                    ~1e-6 eps-MSE on the nets).
+                                    (1 was a split-bf16 mode in rounds 1-2; removed) */
     int64_t x0s[5], x1s[5], ys[5], rs[5];   /* element strides (b,c,d,h,w) */
 } SdcConvDesc;
 
@@ -109,14 +127,15 @@ int sdc_conv(const SdcConvDesc* d, const float* x0, const float* x1, const float
  * (1x1, strided, sub-pixel), are split over up to 8 workgroups per output tile, the partial outputs
  * go to `work` (sdc_conv_splitk_bytes(d) bytes, 16-byte aligned; 0 = this conv is not split: the call is then exactly sdc_conv) and
  * are summed in split order -- deterministic, but the split depends on the batch, so a sample's rounding depends on the batch it
- * rides in: the samplers use sdc_conv only unless the caller opts in (net.split_small_grids).  No fused residual. */
+ * rides in: the samplers use sdc_conv only unless the caller opts in (net.split_small_grids).  No fused residual.  Precision 6 / 7:
+ * precision 4's split kernels on the buffer's precision-4 prefix (fp32; the fp16 kernel never splits K). */
 size_t sdc_conv_splitk_bytes(const SdcConvDesc* d);
 int sdc_conv_splitk(const SdcConvDesc* d, const float* x0, const float* x1, const float* wp, const float* bias, float* y,
                     float* work, size_t work_bytes, void* stream);
 
 /* Host-side query (measurement tooling, launches nothing): which kernel template instance sdc_conv would run for this
  * descriptor, and the share of the direct-form multiply-adds 2*B*P*Cout*Cin*taps that it issues on the matrix cores
- * (1 for the direct kernels, 2/3 for Winograd F(2,3) along W, 4/9 for F(2x2,3x3), 8/27 for F(2x2x2,3x3x3)). */
+ * (1 for the direct kernels and conv_f16_kernel, 2/3 for Winograd F(2,3) along W, 4/9 for F(2x2,3x3), 8/27 for F(2x2x2,3x3x3)). */
 int sdc_conv_describe(const SdcConvDesc* d, char* name, size_t cap, double* mfma_share);
 
 /* Conv + GroupNorm statistics of its output in one pass (the Block.proj -> Block.norm pair, 1D/model/unet.py:132-141,
@@ -353,10 +372,11 @@ size_t sdc_chan_norm_bwd_bytes(int B, int C, int64_t S);
 int sdc_chan_norm_bwd(const float* x, const float* gy, const float* g, float* gx, float* gpart, int B, int C, int64_t S,
                       int mode, float eps, void* stream);
 
-/* Kernel layout of an nn.Conv weight w (Cout, Cin, kD, kH, kW) for SdcConvDesc.precision (0, 2, 3, 4, 5) in one launch: Wp followed
+/* Kernel layout of an nn.Conv weight w (Cout, Cin, kD, kH, kW) for SdcConvDesc.precision (0, 2 ... 7) in one launch: Wp followed
  * by the Winograd taps the precision / tap shape call for (layouts: SdcConvDesc.precision above), transformed taps summed in fp64
  * and rounded once.  flip != 0 packs the DATA-GRADIENT weight of the same conv instead (channels transposed, taps flipped; then the
- * arguments Cout / Cin are those of the packed weight, i.e. swapped).  out holds sdc_pack_conv_weight_floats(...) floats. */
+ * arguments Cout / Cin are those of the packed weight, i.e. swapped; not with precision 6 / 7, whose fp16 tail -- a second launch,
+ * RNE -- only the samplers read).  out holds sdc_pack_conv_weight_floats(...) floats. */
 size_t sdc_pack_conv_weight_floats(int Cout, int Cin, int kD, int kH, int kW, int precision);
 int sdc_pack_conv_weight(const float* w, float* out, int Cout, int Cin, int kD, int kH, int kW, int precision, int flip, void* stream);
 
@@ -365,7 +385,8 @@ int sdc_pack_conv_weight(const float* w, float* out, int Cout, int Cin, int kD, 
  * between forwards).  The caller fills w, out, Cout, Cin, kD, kH, kW, precision, flip of every item (meaning as in
  * sdc_pack_conv_weight; out holds sdc_pack_conv_weight_floats(...) floats); sdc_pack_batch_plan (host only, no GPU call)
  * fills the remaining fields and returns the launch size; the caller copies the table to device memory once and calls
- * sdc_pack_batch_run(table_dev, ...) whenever the weights changed.  Results are those of sdc_pack_conv_weight bit for bit. */
+ * sdc_pack_batch_run(table_dev, ...) whenever the weights changed.  Results are those of sdc_pack_conv_weight bit for bit.
+ * Precisions 0 ... 5 (training never asks for the sampler-only 6 / 7: SDC_EINVAL). */
 typedef struct SdcPackItem {
     const float* w;
     float* out;

@@ -440,7 +440,8 @@ class Trainer:
 
     def __init__(self, net):
         self.net = net
-        self.prec = net.precision
+        # precisions 6 / 7 are sampler-only modes (fp16 conv operands): fine-tuning runs precision 4's fp32 kernels, bit for bit
+        self.prec = 4 if net.precision in (6, 7) else net.precision
         self.arena = grad_ops.PackArena()
 
     @contextlib.contextmanager

@@ -93,4 +93,13 @@ bool wg2s_ok(const SdcConvDesc& d, bool small, bool rowhalo);
 int launch_wg2s(const ConvArgs& a, hipStream_t s);
 int launch_wg3s(const ConvArgs& a, hipStream_t s);
 
+// defined in sdc_conv_f16.hip (precision 6)
+int f16_kc(int kD, int kH, int kW);           // channel chunk of the fp16 weight tail for this tap shape (0: no tail)
+bool f16_faster(const SdcConvDesc& d);        // the measured dispatch table: shapes where the fp16 kernel beats precision 4's
+bool f16_ok(const SdcConvDesc& d);            // conv_f16_kernel covers this descriptor (includes f16_faster)
+int f16_gnparts(const SdcConvDesc& d, int G);
+const char* f16_name(const SdcConvDesc& d);
+int launch_f16(const ConvArgs& a, const _Float16* wh, hipStream_t s);
+int pack_f16_tail(const float* w, float* tail, int64_t gap, int Cout, int Cin, int kD, int kH, int kW, hipStream_t s);
+
 }  // namespace sdcconv

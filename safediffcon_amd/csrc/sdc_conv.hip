@@ -1742,6 +1742,7 @@ extern "C" int sdc_conv(const SdcConvDesc* dp, const float* x0, const float* x1,
 extern "C" size_t sdc_conv_splitk_bytes(const SdcConvDesc* dp) {
     if (!dp) return 0;                               // (every form below checks the precision it needs itself; the direct forms need none)
     static const int no_rh = exp_env("SDC_NO_ROWHALO");
+    if (dp->precision == 6 || dp->precision == 7) { SdcConvDesc d4 = *dp; d4.precision = 4; return sdc_conv_splitk_bytes(&d4); }   // (precision 4's split kernels)
     const SdcConvDesc& d = *dp;
     if (wg3s_ok(d, conv_small(d), !no_rh) || wg3_ok(d, conv_small(d), !no_rh)) return 0;
     int S;
@@ -1763,6 +1764,11 @@ extern "C" int sdc_conv_splitk(const SdcConvDesc* dp, const float* x0, const flo
 
 extern "C" int sdc_conv_gnparts(const SdcConvDesc* dp, int G) {
     if (!dp) return 0;
+    if (dp->precision == 6 || dp->precision == 7) {
+        if (f16_ok(*dp)) return f16_gnparts(*dp, G);
+        SdcConvDesc d4 = *dp; d4.precision = 4;
+        return sdc_conv_gnparts(&d4, G);
+    }
     static const int no_rh = exp_env("SDC_NO_ROWHALO");
     const int64_t ntot = (int64_t)dp->B * dp->oD * dp->oH * dp->oW;
     static const int no_wg2 = exp_env("SDC_NO_WG2");
@@ -1806,7 +1812,7 @@ int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const flo
     SDC_REQUIRE(d.Cin1 == 0 || x1, SDC_ENULL, "sdc_conv: Cin1 > 0 but x1 is null");
     SDC_REQUIRE(d.kD > 0 && d.kH > 0 && d.kW > 0 && d.sD > 0 && d.sH > 0 && d.sW > 0, SDC_EINVAL,
                 "sdc_conv: bad kernel/stride");
-    SDC_REQUIRE(d.precision == 0 || (d.precision >= 2 && d.precision <= 5), SDC_EINVAL, "sdc_conv: precision must be 0 (fp32 MFMA, direct form), 2 (fp32 Winograd along W), 3 (fp32 Winograd over H and W), 4 (fp32 Winograd over D, H and W) or 5 (as 4, F(4,3) for the 1-D convs)");
+    SDC_REQUIRE(d.precision == 0 || (d.precision >= 2 && d.precision <= 7), SDC_EINVAL, "sdc_conv: precision must be 0 (fp32 MFMA, direct form), 2 (fp32 Winograd along W), 3 (fp32 Winograd over H and W), 4 (fp32 Winograd over D, H and W), 5 (as 4, F(4,3) for the 1-D convs), 6 (as 4, fp16 operands for the 3-tap convs where measured faster) or 7 (as 6 on every covered 3-tap conv)");
     SDC_REQUIRE(!gn_part || d.precision >= 2, SDC_EINVAL, "sdc_conv_gn: fused GroupNorm statistics need precision 2, 3 or 4 (sdc_conv_gnparts returned 0)");
     // the caller sized `parts` with sdc_conv_gnparts(d, G), which sees the descriptor only: a kernel picked here on other
     // grounds (pointer alignment, a residual) with a different part count would write a table the finalize pass misreads
@@ -1851,6 +1857,24 @@ int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const flo
     const bool fast = (d.Cin0 % BK == 0) && (d.Cin1 % BK == 0) && small && d.Cout < (1 << 30);
     hipStream_t s = sdc::as_stream(stream);
     auto even = [](const int64_t* st) { return st[4] == 1 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0 && st[3] % 2 == 0; };
+    // precision 6 / 7: fp16 operands, fp32 accumulation (sdc_conv_f16.hip) for the covered 3-tap convs (6: those of the measured
+    // dispatch table); the other convs, and sdc_conv_splitk, run precision 4's kernels on the buffer's precision-4 prefix
+    if (d.precision == 6 || d.precision == 7) {
+        if (!split_work && f16_ok(d)) {
+            if (gn_part) {
+                a.gn_nparts = f16_gnparts(d, gn_G);
+                SDC_REQUIRE(a.gn_nparts > 0, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
+                SDC_GN_PARTS_AGREE(a.gn_nparts);
+                a.gn_part = gn_part; a.gn_G = gn_G; a.gn_cpg = d.Cout / gn_G; a.gn_S = d.oD * d.oH * d.oW;
+            }
+            SDC_PICK(f16_name(d), 1.0);
+            const size_t off = (sdc_pack_conv_weight_floats(d.Cout, a.Cin, d.kD, d.kH, d.kW, 4) + 3) & ~(size_t)3;   // 16-byte aligned tail
+            return launch_f16(a, reinterpret_cast<const _Float16*>(wp + off), s);
+        }
+        SdcConvDesc d4 = d;
+        d4.precision = 4;
+        return conv_impl(&d4, x0, x1, wp, bias, residual, y, gn_part, gn_G, stream, split_work, split_bytes);
+    }
     static const int no_wg2 = exp_env("SDC_NO_WG2");
     static const int no_wg3 = exp_env("SDC_NO_WG3");
     // fp32 Winograd F(2x2x2,3x3x3), two workgroups per CU (round 5): 3x3x3 stride-1 convs over whole rows, plane pairs

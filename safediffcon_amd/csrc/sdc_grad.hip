@@ -1272,17 +1272,28 @@ void pack_sections(int Cout, int Cin, int kD, int kH, int kW, int precision, int
 }
 }  // namespace
 
+namespace sdcconv {       // sdc_conv_f16.hip
+int f16_kc(int kD, int kH, int kW);
+int pack_f16_tail(const float* w, float* tail, int64_t gap, int Cout, int Cin, int kD, int kH, int kW, hipStream_t s);
+}
+
+// precision 6 / 7: precision 4's sections, then -- for the 1x1x3 / 1x3x3 / 3x3x3 taps -- the fp16 tail Wh[tap][ci / KC][co][ci % KC] (RNE, Cin
+// zero-padded to whole chunks of KC = 32 channels) from the next 16-byte boundary, the gap zero-filled
 extern "C" size_t sdc_pack_conv_weight_floats(int Cout, int Cin, int kD, int kH, int kW, int precision) {
     int64_t n[5];
     pack_sections(Cout, Cin, kD, kH, kW, precision, n);
-    return (size_t)(n[0] + n[1] + n[2] + n[3] + n[4]);
+    const size_t n4 = (size_t)(n[0] + n[1] + n[2] + n[3] + n[4]);
+    const int kc = (precision == 6 || precision == 7) ? sdcconv::f16_kc(kD, kH, kW) : 0;
+    if (!kc) return n4;
+    return ((n4 + 3) & ~(size_t)3) + (size_t)kD * kH * kW * ((Cin + kc - 1) / kc) * kc * Cout / 2;
 }
 
 extern "C" int sdc_pack_conv_weight(const float* w, float* out, int Cout, int Cin, int kD, int kH, int kW, int precision, int flip,
                                     void* stream) {
     SDC_REQUIRE(w && out, SDC_ENULL, "sdc_pack_conv_weight: null pointer");
-    SDC_REQUIRE(Cout > 0 && Cin > 0 && kD > 0 && kH > 0 && kW > 0 && (precision == 0 || (precision >= 2 && precision <= 5)), SDC_EINVAL,
+    SDC_REQUIRE(Cout > 0 && Cin > 0 && kD > 0 && kH > 0 && kW > 0 && (precision == 0 || (precision >= 2 && precision <= 7)), SDC_EINVAL,
                 "sdc_pack_conv_weight: bad arguments");
+    SDC_REQUIRE(precision < 6 || !flip, SDC_EINVAL, "sdc_pack_conv_weight: precisions 6 / 7 are sampler modes: no data-gradient packing");
     PackArgs a;
     a.w = w; a.out = out; a.Cout = Cout; a.Cin = Cin; a.kD = kD; a.kH = kH; a.kW = kW; a.flip = flip;
     int64_t n[5];
@@ -1297,6 +1308,12 @@ extern "C" int sdc_pack_conv_weight(const float* w, float* out, int Cout, int Ci
     SDC_REQUIRE(grid.y < 65536u, SDC_EINVAL, "sdc_pack_conv_weight: too many input channels");
     const unsigned tap_magic = (unsigned)(((1u << 24) + taps - 1) / taps);
     hipLaunchKernelGGL(pack_weight_kernel, grid, dim3(NT), lds, sdc::as_stream(stream), a, co_sh, ci_sh, tap_magic);
+    if ((precision == 6 || precision == 7) && sdcconv::f16_kc(kD, kH, kW)) {
+        { const int rc = sdc::check_launch("sdc_pack_conv_weight"); if (rc) return rc; }
+        const int64_t n4 = n[0] + n[1] + n[2] + n[3] + n[4];
+        return sdcconv::pack_f16_tail(w, out + ((n4 + 3) & ~(int64_t)3), ((n4 + 3) & ~(int64_t)3) - n4, Cout, Cin, kD, kH, kW,
+                                      sdc::as_stream(stream));
+    }
     return sdc::check_launch("sdc_pack_conv_weight");
 }
 

@@ -78,6 +78,13 @@ def pack_conv_weight(t, kind="conv", precision=0):
             return t4.permute(2, 3, 1, 0).reshape(-1, co).contiguous()
         t5 = as5(t)                                       # (Cout, Cin, kD, kH, kW)
         return t5.permute(2, 3, 4, 1, 0).reshape(-1, t5.shape[0]).contiguous()
+    if precision in (6, 7):
+        # precision 4's buffer, zero-padded to 16 bytes, then the fp16 tail of the 3-tap convs (f16_tail_layout)
+        p4 = pack_conv_weight(t, kind, 4)
+        k = tuple(as5(t).shape[2:])
+        if kind != "conv" or f16_kc(k) == 0:
+            return p4
+        return torch.cat([p4, p4.new_zeros(-p4.numel() % 4), f16_tail(t)])
     wp = base().to(torch.float32)
     if precision not in (2, 3, 4, 5) or kind != "conv" or t.shape[-1] != 3:
         return wp
@@ -102,6 +109,31 @@ def pack_conv_weight(t, kind="conv", precision=0):
             u3 = torch.einsum("zd,jh,xk,oidhk->ziojx", G, G, G, t5)
             parts.append(u3.reshape(-1).to(torch.float32))
     return torch.cat(parts)
+
+
+def f16_kc(k):
+    """channel chunk KC of the precision-6 fp16 weight tail for taps k = (kD, kH, kW); 0: that tap shape has no tail"""
+    k = tuple(k)
+    return 32 if tuple(k) in ((1, 1, 3), (1, 3, 3), (3, 3, 3)) else 0
+
+
+def f16_tail(t):
+    """fp16 tail of a precision-6 conv weight (Cout, Cin, *k) (include/sdc.h): Wh[tap][ci // KC][co][ci % KC] = w[co][ci][tap] rounded to
+    fp16 (RNE), Cin zero-padded to whole KC chunks, returned as the float32 words that hold it"""
+    t5 = as5(t).to(torch.float32)
+    co, ci = t5.shape[0], t5.shape[1]
+    kc = f16_kc(t5.shape[2:])
+    nch = (ci + kc - 1) // kc
+    w = t5.permute(2, 3, 4, 1, 0).reshape(-1, ci, co)                     # [tap][ci][co]
+    w = torch.cat([w, w.new_zeros(w.shape[0], nch * kc - ci, co)], 1)      # Cin padded
+    w = w.reshape(w.shape[0], nch, kc, co).permute(0, 1, 3, 2).contiguous()  # [tap][chunk][co][KC]
+    return w.half().reshape(-1).view(torch.float32)
+
+
+def f16_floats(nw4, k, cin, cout):
+    """length in floats of a precision-6 buffer whose precision-4 prefix holds nw4 floats (covered taps k)"""
+    kc = f16_kc(k)
+    return (nw4 + 3) // 4 * 4 + k[0] * k[1] * k[2] * ((cin + kc - 1) // kc) * kc * cout // 2
 
 
 class Pool:
@@ -135,10 +167,12 @@ class Plan:
         self.lib = _lib.get_lib()
         # conv algorithm (include/sdc.h): 0 direct fp32 MFMA | 2 fp32 Winograd F(2,3) along W | 3 F(2x2,3x3) over (H, W) where
         # covered, else as 2 | 4 (default of the nets) F(2x2x2,3x3x3) over (D, H, W) where covered, else as 3 | 5 (opt-in) as 4,
-        # with F(4,3) along W for the (1,1,3) convs (Conv1d k3: half the direct MFMA work at 3x the rounding error)
+        # with F(4,3) along W for the (1,1,3) convs (Conv1d k3: half the direct MFMA work at 3x the rounding error) | 6 (opt-in,
+        # samplers only) as 4, with fp16 operands and fp32 accumulation for the stride-1 pad-1 3-tap convs (csrc/sdc_conv_f16.hip) where
+        # the measured dispatch table has the fp16 kernel ahead | 7 (tests, measurement) as 6 on every covered 3-tap conv
         self.precision = int(precision)
-        if self.precision not in (0, 2, 3, 4, 5):
-            raise ValueError(f"precision must be 0, 2, 3, 4 or 5 (got {precision})")
+        if self.precision not in (0, 2, 3, 4, 5, 6, 7):
+            raise ValueError(f"precision must be 0, 2, 3, 4, 5, 6 or 7 (got {precision})")
         self.calls = []          # (fn, args, keepalive)
         self.pool = Pool(self.device)
         self.keep = []           # descriptors / tensors that must outlive the plan
@@ -222,7 +256,11 @@ class Plan:
         wino43 = wp.dim() == 1 and tuple(k) == (1, 1, 3) and wp.numel() == nw + nw // 3 * 4 + nw // 3 * 6   # precision 5: + F(4,3) taps
         wino2 = wp.dim() == 1 and k[1] == 3 and k[2] == 3 and wp.numel() == nw + nw // 3 * 4 + nw // 9 * 16
         wino3 = wp.dim() == 1 and tuple(k) == (3, 3, 3) and wp.numel() == nw + nw // 3 * 4 + nw // 9 * 16 + nw // 27 * 64
-        assert wino or wino2 or wino3 or wino43 or wp.numel() == nw, (wp.shape, k, c0, c1, cout)
+        n4 = nw + (nw // 3 * 4 if k[2] == 3 else 0) + (nw // 9 * 16 if k[1] == 3 and k[2] == 3 else 0) + (nw // 27 * 64 if tuple(k) == (3, 3, 3) else 0)
+        f16 = self.precision in (6, 7) and wp.dim() == 1 and f16_kc(k) > 0 and wp.numel() == f16_floats(n4, tuple(k), c0 + c1, cout)   # precision 6: + fp16 tail
+        if f16:
+            wino = wino2 = wino3 = wino43 = False
+        assert f16 or wino or wino2 or wino3 or wino43 or wp.numel() == nw, (wp.shape, k, c0, c1, cout)
         d = SdcConvDesc()
         d.B, d.Cin0, d.Cin1, d.Cout = B, c0, c1, cout
         d.iD, d.iH, d.iW = iD, iH, iW
@@ -231,7 +269,7 @@ class Plan:
         d.sD, d.sH, d.sW = stride
         d.pD, d.pH, d.pW = pad
         d.uD, d.uH, d.uW = up
-        d.up_mode, d.precision = up_mode, (5 if wino43 else 4 if wino3 else 3 if wino2 else 2 if wino else 0)
+        d.up_mode, d.precision = up_mode, (self.precision if f16 else 5 if wino43 else 4 if wino3 else 3 if wino2 else 2 if wino else 0)
         d.x0s[:] = _s5(x)
         d.x1s[:] = _s5(x1) if x1 is not None else (0,) * 5
         d.ys[:] = _s5(out)

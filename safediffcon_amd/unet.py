@@ -293,7 +293,10 @@ class _HipUNet(nn.Module):
         # conv algorithm (include/sdc.h): 4 (default) = fp32 Winograd wherever a kernel covers the shape -- F(2x2x2,3x3x3) over
         # (D, H, W) for the 3x3x3 stride-1 convs (8/27 of the direct form's MFMA work), F(2x2,3x3) over (H, W) for the 3x3 ones
         # (4/9), F(2,3) along W for the other 3-tap convs (2/3); 3 = without the depth transform; 2 = F(2,3) along W only;
-        # 0 = fp32 direct everywhere.  All modes are fp32 end to end (rounding order differs).
+        # 0 = fp32 direct everywhere.  These modes are fp32 end to end (rounding order differs).  6 (opt-in, samplers only) = as 4,
+        # with the stride-1 pad-1 3-tap convs on the fp16 matrix pipe where its measured dispatch table has them faster (fp16
+        # operands, fp32 accumulation; ~5e-7 eps-MSE; 7 = the same on every covered conv, a test hook); forward_train and the
+        # differentiable paths keep precision 4.  Set before the first call of a shape (plans are cached per precision).
         self.precision = 4
         # LinearAttention blocks of width 64 / 128 as the fused 3-launch form (csrc/sdc_lablock.hip); False = the
         # unfused chain norm -> 1x1 -> attention core -> 1x1 -> norm (kept for wider layers and for A/B checks)

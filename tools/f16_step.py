@@ -1,0 +1,186 @@
+#!/usr/bin/env python3
+"""Same-box A/B of conv precision 4 (fp32 Winograd) against 6 (fp16 operands on the 3-tap convs, csrc/sdc_conv_f16.hip).
+
+  python tools/f16_step.py [--workloads c4,c2,c3] [--steps 20] [--warmup 5] [--rounds 2] [--arm 6|7]
+      sampler step of bench.workload(..., precision=4 / arm) (bench.py itself unchanged), the two arms interleaved round by round;
+      ms/step with the shader clock and socket power sampled over each timed region (bench.GpuSensors)
+  python tools/f16_step.py --shapes [--workloads ...]
+      every conv of the nets' forward plans that the fp16 kernel covers (precision 7: no dispatch table): sdc_conv / sdc_conv_gn
+      at precision 4 against 7 on the same buffers, median of 20 launches each -- the data of precision 6's dispatch table
+      (csrc/sdc_conv_f16.hip f16_faster)
+  python tools/f16_step.py --drift [T]
+      T-step (default 1000) guided smoke trajectories at production width, B = 2, identical Philox noise, precisions 6 and 7
+      against 4
+"""
+import _libsel  # noqa: F401  (SDC_LIB_PATH -> safediffcon_amd._lib.use_library, tools only)
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+import safediffcon_amd as sdc  # noqa: E402
+from safediffcon_amd import _lib  # noqa: E402
+
+DEV = torch.device("cuda:0")
+
+
+def step_ab(names, steps, warmup, rounds, arm=6):
+    torch.cuda.set_device(DEV)
+    side = torch.cuda.Stream(device=DEV)
+    for name in names:
+        B = bench.DEFAULT_B[name]
+        loops = {}
+        with torch.cuda.stream(side), torch.no_grad():
+            for prec in (4, arm):
+                W = bench.workload(name, None, B, DEV, 0, 1, precision=prec, cal_steps=0)
+                torch.manual_seed(2)
+                S = W["prep"]()
+                S.init()
+                loops[prec] = S
+            res = {4: [], arm: []}
+            for r in range(rounds):
+                for prec in ((4, arm) if r % 2 == 0 else (arm, 4)):
+                    S = loops[prec]
+
+                    def run(n):
+                        for _ in range(n):
+                            if S.t_host < (0 if S.impose_last else 1):
+                                S.init()
+                            S.step()
+                    run(warmup)
+                    torch.cuda.synchronize()
+                    sens = bench.GpuSensors(0)
+                    sens.start()
+                    t0 = time.perf_counter()
+                    run(steps)
+                    torch.cuda.synchronize()
+                    ms = (time.perf_counter() - t0) * 1e3 / steps
+                    ck = sens.stop() or {}
+                    res[prec].append(ms)
+                    print(f"[measured] {name} B={B} precision {prec} round {r}: {ms:.2f} ms/step  sclk median "
+                          f"{ck.get('sclk_mhz_median')} MHz (min {ck.get('sclk_mhz_min')})  power mean {ck.get('power_w_mean')} W "
+                          f"(max {ck.get('power_w_max')})", flush=True)
+            m4, mx = statistics.median(res[4]), statistics.median(res[arm])
+            print(f"[measured] {name}: precision {arm} / 4 = {mx:.2f} / {m4:.2f} ms/step = {mx / m4:.3f}", flush=True)
+            for S in loops.values():
+                S.close()
+        del loops
+        torch.cuda.empty_cache()
+
+
+def _time_call(fn, args, stream, n=20):
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for _ in range(3):
+        _lib.check(fn(*args, stream), fn.__name__)
+    ts = []
+    for a, b in evs:
+        a.record()
+        _lib.check(fn(*args, stream), fn.__name__)
+        b.record()
+    torch.cuda.synchronize()
+    for a, b in evs:
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def shapes(names):
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    nets = {
+        "c4": (lambda: sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7), (64, 32, 7, 64, 64)),
+        "c2": (lambda: sdc.Unet2D(dim=64, dim_mults=(1, 2, 4, 8), channels=3, resnet_block_groups=1), (256, 3, 16, 128)),
+        "c3": (lambda: sdc.Unet1D(dim=256, dim_mults=(1, 2, 4, 8), channels=12, resnet_block_groups=1), (128, 12, 128)),
+    }
+    name_buf = C.create_string_buffer(96)
+    share = C.c_double(0.0)
+    for wl in names:
+        make, shape = nets[wl]
+        torch.manual_seed(0)
+        net = make().to(DEV)
+        net.precision = 7
+        x = torch.randn(shape, device=DEV) * 0.5
+        t = torch.full((shape[0],), 500, device=DEV, dtype=torch.long)
+        with torch.no_grad():
+            net(x, t)
+            plan = net.entry(tuple(shape), shape[0])["plan"]
+        seen, tot4, tot7 = set(), 0.0, 0.0
+        for fn, args in plan.calls:
+            if fn.__name__ not in ("sdc_conv", "sdc_conv_gn"):
+                continue
+            d6 = args[0]._obj
+            lib.sdc_conv_describe(C.byref(d6), name_buf, 96, C.byref(share))
+            kname = name_buf.value.decode()
+            if "f16" not in kname:
+                continue
+            key = (d6.kD, d6.kH, d6.kW, d6.Cin0, d6.Cin1, d6.Cout, d6.B, d6.oD, d6.oH, d6.oW, d6.rs[1] != 0, fn.__name__)
+            d4 = type(d6).from_buffer_copy(d6)
+            d4.precision = 4
+            lib.sdc_conv_describe(C.byref(d4), name_buf, 96, C.byref(share))
+            k4name = name_buf.value.decode()
+            ms = {}
+            for prec, d in ((4, d4), (7, d6)):
+                if fn.__name__ == "sdc_conv_gn":
+                    G = args[8]
+                    nparts = int(lib.sdc_conv_gnparts(C.byref(d), G))
+                    if nparts > 0:
+                        parts = torch.empty(d.B * G * nparts * 2, dtype=torch.float64, device=DEV)
+                        ms[prec] = _time_call(lib.sdc_conv_gn, (C.byref(d), *args[1:7], parts.data_ptr(), G), stream)
+                        continue
+                ms[prec] = _time_call(lib.sdc_conv, (C.byref(d), *args[1:7]), stream)
+            flop = 2.0 * d6.B * d6.oD * d6.oH * d6.oW * d6.Cout * (d6.Cin0 + d6.Cin1) * d6.kD * d6.kH * d6.kW
+            tot4 += ms[4]
+            tot7 += ms[7]
+            tag = "" if key not in seen else " (repeat)"
+            seen.add(key)
+            print(f"[measured] {wl} {d6.kD}x{d6.kH}x{d6.kW} Cin {d6.Cin0}+{d6.Cin1} Cout {d6.Cout} B {d6.B} {d6.oD}x{d6.oH}x{d6.oW} "
+                  f"res {int(d6.rs[1] != 0)} {fn.__name__}: p4 {k4name} {ms[4] * 1e3:.1f} us | p7 {kname} {ms[7] * 1e3:.1f} us "
+                  f"({flop / ms[7] / 1e9:.0f} TFLOP/s direct-form) -> x{ms[4] / ms[7]:.2f}{tag}", flush=True)
+        print(f"[measured] {wl}: the fp16-covered convs of one forward: p4 {tot4:.2f} ms, p7 {tot7:.2f} ms", flush=True)
+        del net, plan
+        torch.cuda.empty_cache()
+
+
+def drift(T):
+    torch.manual_seed(0)
+    net = sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7).to(DEV)
+    init = (torch.rand(2, 64, 64) * 0.2).to(DEV)
+    control = (torch.randn(2, 32, 2, 64, 64) * 0.3).to(DEV)
+    outs = {}
+    for prec in (4, 6, 7):
+        net.precision = prec
+        gs = sdc.GaussianDiffusionSmoke(net, image_size=64, frames=32, timesteps=T, standard_fixed_ratio=100.0).to(DEV)
+        torch.manual_seed(7)
+        t0 = time.perf_counter()
+        outs[prec] = gs.sample(batch_size=2, design_fn=sdc.SmokeGuidance(0.01, 0.9, 0.1), init=init, control=control).cpu()
+        print(f"precision {prec}: {time.perf_counter() - t0:.1f} s, finite {bool(torch.isfinite(outs[prec]).all())}, "
+              f"|x|max {outs[prec].abs().max():.3f}", flush=True)
+    for p in (6, 7):
+        d = (outs[p] - outs[4]).abs()
+        print(f"[measured] {T}-step guided smoke trajectories, precision {p} vs 4: max|diff| {d.max():.3e}  mean|diff| {d.mean():.3e}  "
+              f"MSE {(d ** 2).mean():.3e}", flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="c4,c2,c3")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--arm", type=int, default=6, choices=(6, 7), help="the precision timed against 4")
+    ap.add_argument("--shapes", action="store_true")
+    ap.add_argument("--drift", type=int, nargs="?", const=1000, default=None)
+    a = ap.parse_args()
+    wls = [w for w in a.workloads.split(",") if w]
+    if a.drift:
+        drift(a.drift)
+    elif a.shapes:
+        shapes(wls)
+    else:
+        step_ab(wls, a.steps, a.warmup, a.rounds, a.arm)

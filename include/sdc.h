@@ -110,6 +110,7 @@ typedef struct SdcConvDesc {
                                         sdc_conv_gn are fused where S % 256 == 0 or whole samples of 64 / 128 positions share a tile.
                                     7 = test and measurement hook, not a user mode: 6 without the dispatch table (every conv the fp16
                                         kernel covers), the same buffer.
+                                    (8 is a packing code only, sdc_pack_conv_weight: the fine-tuning layout, read with precision 6 / 7)
                                     Rounding of 6 / 7: fp16 x fp16 products are exact in fp32, so the result is an fp64 conv of the
                                     rounded operands up to fp32 summation order (~2e-4 of the output rms from the operand rounding;
                                     ~1e-6 eps-MSE on the nets).
@@ -345,12 +346,42 @@ typedef struct SdcWgradDesc {
     int32_t sD, sH, sW;
     int32_t pD, pH, pW;
     int32_t uD, uH, uW;
-    int32_t _pad;
+    int32_t precision;           /* sdc_conv_wgrad: unread (0); sdc_conv_wgrad_f16: 6 or 7, below */
     int64_t gs[5], xs[5];        /* element strides (b, c, d, h, w) of G and X */
 } SdcWgradDesc;
 size_t sdc_conv_wgrad_bytes(const SdcWgradDesc* d);
 int sdc_conv_wgrad(const SdcWgradDesc* d, const float* g, const float* x, float* dw, float* dbias, void* work,
                    size_t work_bytes, void* stream);
+
+/* Fine-tuning with fp16 operands (net.train_precision 6 / 7, opt-in).  For the stride-1 pad-1 3-tap convs
+ * (1x1x3, 1x3x3, 3x3x3) the three directions run on the fp16 matrix pipe with fp32 accumulation:
+ *   forward         sdc_conv at SdcConvDesc.precision 6 / 7 on a precision-8 buffer (below), as the samplers do;
+ *   data gradient   sdc_conv_dgrad_f16 on the precision-8 buffer of the data-gradient weight (flip = 1);
+ *   weight gradient sdc_conv_wgrad_f16.
+ * The loss gradient G of a conv (per-element ~1e-7 for a mean loss: below fp16's normal range) is scaled per tensor by 2^e before it
+ * is rounded and the results by 2^-e (both exact); e is computed on the device, so a step stays capturable and never syncs.
+ *
+ * sdc_f16_grad_exponent: e[0] = e such that max|G| 2^e lies in [2^14, 2^15), 0 when max|G| is 0 or not finite (inf / NaN then
+ * reach dx / dw unchanged), clamped to [-126, 126].  G is (B, C, D, H, W) through strides[5] (elements); e holds SDC_F16_EXP_INTS
+ * int32 of device memory (e[1 ...]: scratch).  Two launches. */
+#define SDC_F16_EXP_INTS 1025
+int sdc_f16_grad_exponent(const float* g, int B, int C, int D, int H, int W, const int64_t* strides, int32_t* e, void* stream);
+
+/* Data gradient dx = conv(g, flipped w): the descriptor of that conv (Cin0 = channels of g, Cout = channels of dx, pad k - 1 - p),
+ * precision 6 (dispatch table of sdc_conv) or 7 (every covered conv), wp a precision-8 flip = 1 buffer.  Where sdc_conv would run
+ * conv_f16_kernel, g is multiplied by 2^e[0] as it is rounded and the accumulators by 2^-e[0]; elsewhere exactly sdc_conv (e unread). */
+int sdc_conv_dgrad_f16(const SdcConvDesc* d, const float* g, const float* wp, const int32_t* e, float* dx, void* stream);
+
+/* Weight gradient of sdc_conv_wgrad with fp16 operands: dw = 2^-e sum fp16(2^e G) fp16(X), fp32 accumulation, positions split over
+ * workgroups and summed in a fixed order (deterministic, no atomics); dbias = fp32 sum of the unscaled G (fixed order).  d.precision
+ * 6: wgrad_f16_kernel where its measured dispatch table (csrc/sdc_wgrad_f16.hip wf_faster, keyed on per-sample sizes) has it ahead
+ * of sdc_conv_wgrad; 7: every covered descriptor (1x1x3 / 1x3x3 / 3x3x3 taps, stride 1, pad 1, rows of 16 / 32 / 64 / 128 positions,
+ * whole rows per 128-position stage).  Other descriptors: exactly sdc_conv_wgrad (e unread).  work: sdc_conv_wgrad_f16_bytes(d)
+ * bytes.  sdc_conv_wgrad_describe names the kernel a descriptor runs (host only, launches nothing). */
+size_t sdc_conv_wgrad_f16_bytes(const SdcWgradDesc* d);
+int sdc_conv_wgrad_f16(const SdcWgradDesc* d, const float* g, const float* x, const int32_t* e, float* dw, float* dbias, void* work,
+                       size_t work_bytes, void* stream);
+int sdc_conv_wgrad_describe(const SdcWgradDesc* d, char* name, size_t cap);
 
 /* Backward of sdc_gn_apply (GroupNorm -> (scale+1, shift) -> SiLU; Block, conv3d.py:189-204, 1D/model/unet.py:128-147):
  * h = the conv output the forward normalised (contiguous (B,C,S)), stats from the forward, ss = per-sample rows
@@ -376,7 +407,9 @@ int sdc_chan_norm_bwd(const float* x, const float* gy, const float* g, float* gx
  * by the Winograd taps the precision / tap shape call for (layouts: SdcConvDesc.precision above), transformed taps summed in fp64
  * and rounded once.  flip != 0 packs the DATA-GRADIENT weight of the same conv instead (channels transposed, taps flipped; then the
  * arguments Cout / Cin are those of the packed weight, i.e. swapped; not with precision 6 / 7, whose fp16 tail -- a second launch,
- * RNE -- only the samplers read).  out holds sdc_pack_conv_weight_floats(...) floats. */
+ * RNE -- only the samplers read).  precision 8 = the fine-tuning layout of precisions 6 / 7: precision 6's buffer (the precision-4
+ * sections, then for the 1x1x3 / 1x3x3 / 3x3x3 taps the fp16 tail) written by the one launch, flip allowed (the tail then holds the
+ * flipped, transposed taps); sdc_conv reads it with SdcConvDesc.precision 6 or 7.  out holds sdc_pack_conv_weight_floats(...) floats. */
 size_t sdc_pack_conv_weight_floats(int Cout, int Cin, int kD, int kH, int kW, int precision);
 int sdc_pack_conv_weight(const float* w, float* out, int Cout, int Cin, int kD, int kH, int kW, int precision, int flip, void* stream);
 
@@ -386,7 +419,7 @@ int sdc_pack_conv_weight(const float* w, float* out, int Cout, int Cin, int kD, 
  * sdc_pack_conv_weight; out holds sdc_pack_conv_weight_floats(...) floats); sdc_pack_batch_plan (host only, no GPU call)
  * fills the remaining fields and returns the launch size; the caller copies the table to device memory once and calls
  * sdc_pack_batch_run(table_dev, ...) whenever the weights changed.  Results are those of sdc_pack_conv_weight bit for bit.
- * Precisions 0 ... 5 (training never asks for the sampler-only 6 / 7: SDC_EINVAL). */
+ * Precisions 0, 2 ... 5 and the fine-tuning layout 8 (the sampler-only 6 / 7: SDC_EINVAL). */
 typedef struct SdcPackItem {
     const float* w;
     float* out;

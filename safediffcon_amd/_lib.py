@@ -33,7 +33,7 @@ class SdcStepDesc(C.Structure):
 class SdcWgradDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "B", "M", "N", "oD", "oH", "oW", "iD", "iH", "iW", "kD", "kH", "kW", "sD", "sH", "sW", "pD", "pH", "pW",
-        "uD", "uH", "uW", "_pad")] + [("gs", C.c_int64 * 5), ("xs", C.c_int64 * 5)]
+        "uD", "uH", "uW", "precision")] + [("gs", C.c_int64 * 5), ("xs", C.c_int64 * 5)]
 
 
 class SdcPackItem(C.Structure):
@@ -101,6 +101,11 @@ SIGNATURES = {
                                       C.c_float, C.c_float, C.c_float, _stream]),
     "sdc_conv_wgrad_bytes": (C.c_size_t, [C.POINTER(SdcWgradDesc)]),
     "sdc_conv_wgrad": (C.c_int, [C.POINTER(SdcWgradDesc), _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_size_t, _stream]),
+    "sdc_f16_grad_exponent": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _stream]),
+    "sdc_conv_dgrad_f16": (C.c_int, [C.POINTER(SdcConvDesc), _f32p, _f32p, C.c_void_p, _f32p, _stream]),
+    "sdc_conv_wgrad_f16_bytes": (C.c_size_t, [C.POINTER(SdcWgradDesc)]),
+    "sdc_conv_wgrad_f16": (C.c_int, [C.POINTER(SdcWgradDesc), _f32p, _f32p, C.c_void_p, _f32p, _f32p, C.c_void_p, C.c_size_t, _stream]),
+    "sdc_conv_wgrad_describe": (C.c_int, [C.POINTER(SdcWgradDesc), C.c_char_p, C.c_size_t]),
     "sdc_gn_silu_bwd_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, _i64]),
     "sdc_gn_silu_bwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _i64, _f32p, _f32p, _f32p, _f32p, _f32p,
                                   C.c_int, C.c_int, C.c_int, _i64, _stream]),

@@ -46,8 +46,11 @@ def _stream(t):
 
 
 # --------------------------------------------------------------------------------------------------- raw conv launch
-def conv_raw(x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), up_mode=0, out=None, residual=None):
-    """one sdc_conv launch on torch's current stream (the eager twin of engine.Plan.conv); 5-D views, any strides"""
+def conv_raw(x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), up_mode=0, out=None, residual=None,
+             prec=None, gexp=None):
+    """one sdc_conv launch on torch's current stream (the eager twin of engine.Plan.conv); 5-D views, any strides.
+    prec 6 / 7 (fine-tuning with fp16 operands): wp is a precision-8 buffer (sdc_pack_conv_weight); gexp: the data-gradient form,
+    x is a loss gradient scaled by 2^gexp[0] where the fp16 kernel runs (sdc_conv_dgrad_f16)"""
     lib = _lib.get_lib()
     B, c0, iD, iH, iW = x.shape
     c1 = 0 if x1 is None else x1.shape[1]
@@ -61,13 +64,16 @@ def conv_raw(x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), 
                           dtype=torch.float32, device=x.device)
     nw = k[0] * k[1] * k[2] * (c0 + c1) * cout
     n = wp.numel()
-    prec = 0
-    if k[2] == 3 and n != nw:
+    if prec is not None:
+        assert prec in (6, 7) and n == int(lib.sdc_pack_conv_weight_floats(cout, c0 + c1, *k, 8)), (prec, n, k, c0, c1, cout)
+    elif k[2] == 3 and n != nw:
+        prec = 0
         prec = 2 if n == nw + nw // 3 * 4 else (3 if n == nw + nw // 3 * 4 + nw // 9 * 16 else 4)
         if tuple(k) == (1, 1, 3) and n == nw + nw // 3 * 4 + nw // 3 * 6:
             prec = 5                                                     # 1-D conv packed with its F(4,3) taps
         assert prec != 4 or n == nw + nw // 3 * 4 + nw // 9 * 16 + nw // 27 * 64, (n, nw)
     else:
+        prec = 0
         assert n == nw, (n, nw, k, c0, c1, cout)
     d = SdcConvDesc()
     d.B, d.Cin0, d.Cin1, d.Cout = B, c0, c1, cout
@@ -83,6 +89,16 @@ def conv_raw(x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), 
     d.ys[:] = tuple(int(s) for s in out.stride())
     d.rs[:] = tuple(int(s) for s in residual.stride()) if residual is not None else (0,) * 5
     p = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+    split_wins = prec == 6 and SPLIT_SMALL_GRIDS and residual is None and not getattr(_BATCH_INVARIANT, "on", False) \
+        and int(lib.sdc_conv_splitk_bytes(C.byref(d))) > 0
+    if prec in (6, 7) and not split_wins and conv_kernel(d).startswith("conv_f16"):
+        # the fp16 kernel never splits its input channels; at 6 a conv whose grid precision 4 splits (a small-grid fine-tuning
+        # batch) keeps the split fp32 kernels
+        if gexp is not None:
+            check(lib.sdc_conv_dgrad_f16(C.byref(d), p(x), p(wp), gexp.data_ptr(), p(out), _stream(x)), "sdc_conv_dgrad_f16")
+        else:
+            check(lib.sdc_conv(C.byref(d), p(x), p(x1), p(wp), p(bias), p(residual), p(out), _stream(x)), "sdc_conv")
+        return out
     # the fine-tuning step's batch leaves the deep 3x3 convs of the Burgers net on 32-128 workgroups: the input channels are then
     # split over several workgroups per tile (sdc_conv_splitk; the samplers never split -- a sample's rounding would depend on
     # the batch it rides in)
@@ -94,6 +110,33 @@ def conv_raw(x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), 
         return out
     check(lib.sdc_conv(C.byref(d), p(x), p(x1), p(wp), p(bias), p(residual), p(out), _stream(x)), "sdc_conv")
     return out
+
+
+def conv_kernel(d):
+    """name of the kernel sdc_conv runs for descriptor d (sdc_conv_describe; host only)"""
+    buf = C.create_string_buffer(96)
+    check(_lib.get_lib().sdc_conv_describe(C.byref(d), buf, 96, None), "sdc_conv_describe")
+    return buf.value.decode()
+
+
+TRAIN_PRECISIONS = (None, 6, 7)
+
+
+def check_train_precision(v):
+    """net.train_precision: None (fp32 fine-tuning, the default), 6 (fp16 operands for the stride-1 pad-1 3-tap convs in all three
+    directions, where measured faster) or 7 (the same on every covered conv: a test hook); anything else raises ValueError"""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, int) or v not in (6, 7):
+        raise ValueError(f"train_precision must be None, 6 or 7 (got {v!r})")
+    return int(v)
+
+
+def f16_train_form(k, stride, pad, up):
+    """the conv forms train_precision 6 / 7 route to the fp16 kernels: 1x1x3 / 1x3x3 / 3x3x3 taps, stride 1, pad 1 along every
+    3-wide axis, no folded upsampling (the kernels' own coverage -- row widths, LDS -- is checked by the library)"""
+    return (tuple(k) in ((1, 1, 3), (1, 3, 3), (3, 3, 3)) and tuple(stride) == (1, 1, 1) and tuple(up) == (1, 1, 1)
+            and tuple(pad) == tuple(kk // 2 for kk in k))
 
 
 _BATCH_INVARIANT = threading.local()
@@ -176,6 +219,9 @@ class ConvFn(Function):
         bb = None if b is None else b.detach().contiguous()
         wd = w.detach()
         ctx.arena = arena = _ARENA.cur if (_ARENA.cur is not None and grad_ops.PackArena.cacheable(w)) else None
+        if kind == "conv" and prec in (6, 7):
+            return conv_raw(x, grad_ops.pack_conv_weight(wd, 8, arena=arena), bb, w.shape[0], _k5(w), x1=x1, stride=stride, pad=pad, up=up,
+                            prec=prec)
         if kind == "conv":
             return conv_raw(x, grad_ops.pack_conv_weight(wd, prec, arena=arena), bb, w.shape[0], _k5(w), x1=x1, stride=stride, pad=pad, up=up)
         if kind == "convT422":
@@ -195,20 +241,30 @@ class ConvFn(Function):
         c0 = x.shape[1]
         if kind == "conv":
             fork = None
+            f16 = prec in (6, 7)
+            # fp16 operands: the power-of-two scale of gy, once per node, on the node's stream before the fork
+            e = grad_ops.f16_grad_exponent(gy) if f16 else None
+            wkw = dict(precision=prec, exp=e) if f16 else {}
             if need_w or ctx.has_bias:
                 if OVERLAP_WGRAD and (need_x or need_x1):
                     main = torch.cuda.current_stream(gy.device)
                     fork = _side_stream(gy.device)
                     fork.wait_stream(main)
+                    if e is not None:
+                        e.record_stream(fork)
                 with torch.cuda.stream(fork) if fork is not None else contextlib.nullcontext():
-                    gw, gb = grad_ops.conv_wgrad(gy, x, k, stride, pad, up, bias=ctx.has_bias)
+                    gw, gb = grad_ops.conv_wgrad(gy, x, k, stride, pad, up, bias=ctx.has_bias, **wkw)
                     if x1 is not None:
-                        gw1, _ = grad_ops.conv_wgrad(gy, x1, k, stride, pad, up, bias=False)
+                        gw1, _ = grad_ops.conv_wgrad(gy, x1, k, stride, pad, up, bias=False, **wkw)
                         gw = torch.cat((gw, gw1), dim=1)
                     gw = gw.reshape(w.shape)
             if need_x or need_x1:
                 w5 = as5(wd)
-                if stride == (1, 1, 1):
+                if f16:
+                    # the same on the fp16 kernel with a scaled gy (precision-8 flipped buffer; stride 1, no upsampling)
+                    ga = conv_raw(gy, grad_ops.pack_conv_weight(w5, 8, flip=True, arena=ctx.arena), None, w5.shape[1], k,
+                                  pad=tuple(kk - 1 - p for kk, p in zip(k, pad)), prec=prec, gexp=e)
+                elif stride == (1, 1, 1):
                     # correlation with the flipped, transposed taps; pad k - 1 - p restores the input size
                     ga = conv_raw(gy, grad_ops.pack_conv_weight(w5, prec, flip=True, arena=ctx.arena), None, w5.shape[1], k,
                                   pad=tuple(kk - 1 - p for kk, p in zip(k, pad)))
@@ -443,10 +499,12 @@ class Trainer:
         # precisions 6 / 7 are sampler-only modes (fp16 conv operands): fine-tuning runs precision 4's fp32 kernels, bit for bit
         self.prec = 4 if net.precision in (6, 7) else net.precision
         self.arena = grad_ops.PackArena()
+        self.tprec = None        # net.train_precision, read at the start of every training forward (step)
 
     @contextlib.contextmanager
     def step(self, device):
         """one training forward: every packed conv weight refreshed by one launch, conv nodes bound to this net's arena"""
+        self.tprec = check_train_precision(getattr(self.net, "train_precision", None))
         self.arena.begin(device)
         prev, _ARENA.cur = _ARENA.cur, self.arena
         try:
@@ -463,7 +521,10 @@ class Trainer:
         b = self.P(f"{prefix}.bias") if bias else None
         if pad is None:
             pad = tuple(kk // 2 for kk in _k5(w))
-        return ConvFn.apply(x, x1, w, b, (kind, tuple(stride), tuple(pad), tuple(up), self.prec))
+        prec = self.prec
+        if self.tprec is not None and kind == "conv" and f16_train_form(_k5(w), stride, pad, up):
+            prec = self.tprec
+        return ConvFn.apply(x, x1, w, b, (kind, tuple(stride), tuple(pad), tuple(up), prec))
 
     def gn(self, prefix, h, ss=None, residual=None):
         return GNSiLUFn.apply(h, self.P(f"{prefix}.weight"), self.P(f"{prefix}.bias"), ss, residual, self.net.groups)

@@ -99,7 +99,7 @@ bool f16_faster(const SdcConvDesc& d);        // the measured dispatch table: sh
 bool f16_ok(const SdcConvDesc& d);            // conv_f16_kernel covers this descriptor (includes f16_faster)
 int f16_gnparts(const SdcConvDesc& d, int G);
 const char* f16_name(const SdcConvDesc& d);
-int launch_f16(const ConvArgs& a, const _Float16* wh, hipStream_t s);
+int launch_f16(const ConvArgs& a, const _Float16* wh, hipStream_t s, const int32_t* gexp = nullptr);   // gexp: scaled (data-gradient) form
 int pack_f16_tail(const float* w, float* tail, int64_t gap, int Cout, int Cin, int kD, int kH, int kW, hipStream_t s);
 
 }  // namespace sdcconv

@@ -1727,13 +1727,23 @@ __global__ __launch_bounds__(256) void splitk_sum_kernel(const float* __restrict
 }
 
 int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const float* wp, const float* bias,
-              const float* residual, float* y, double* gn_part, int gn_G, void* stream, float* split_work = nullptr, size_t split_bytes = 0);
+              const float* residual, float* y, double* gn_part, int gn_G, void* stream, float* split_work = nullptr, size_t split_bytes = 0,
+              const int32_t* gexp = nullptr);
 
 }  // namespace
 
 extern "C" int sdc_conv(const SdcConvDesc* dp, const float* x0, const float* x1, const float* wp, const float* bias,
                         const float* residual, float* y, void* stream) {
     return conv_impl(dp, x0, x1, wp, bias, residual, y, nullptr, 0, stream);
+}
+
+// data gradient of a fine-tuning conv at precision 6 / 7 (include/sdc.h): the flipped conv of the loss gradient g; where the fp16 kernel
+// runs, g is scaled by 2^e as it is rounded and the result by 2^-e; elsewhere exactly sdc_conv (e unread)
+extern "C" int sdc_conv_dgrad_f16(const SdcConvDesc* dp, const float* g, const float* wp, const int32_t* e, float* dx, void* stream) {
+    SDC_REQUIRE(dp && e, SDC_ENULL, "sdc_conv_dgrad_f16: null pointer");
+    SDC_REQUIRE((dp->precision == 6 || dp->precision == 7) && dp->Cin1 == 0, SDC_EINVAL,
+                "sdc_conv_dgrad_f16: precision 6 or 7, one input");
+    return conv_impl(dp, g, nullptr, wp, nullptr, nullptr, dx, nullptr, 0, stream, nullptr, 0, e);
 }
 
 // Same conv as sdc_conv (no fused residual), for grids that leave most CUs idle -- the fine-tuning step at batch 64 runs the deep
@@ -1805,7 +1815,8 @@ extern "C" int sdc_conv_describe(const SdcConvDesc* dp, char* name, size_t cap, 
 namespace {
 
 int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const float* wp, const float* bias,
-              const float* residual, float* y, double* gn_part, int gn_G, void* stream, float* split_work, size_t split_bytes) {
+              const float* residual, float* y, double* gn_part, int gn_G, void* stream, float* split_work, size_t split_bytes,
+              const int32_t* gexp) {
     SDC_REQUIRE(dp && x0 && wp && y, SDC_ENULL, "sdc_conv: null pointer");
     const SdcConvDesc& d = *dp;
     SDC_REQUIRE(d.B > 0 && d.Cin0 > 0 && d.Cin1 >= 0 && d.Cout > 0, SDC_EINVAL, "sdc_conv: bad channel/batch counts");
@@ -1869,7 +1880,7 @@ int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const flo
             }
             SDC_PICK(f16_name(d), 1.0);
             const size_t off = (sdc_pack_conv_weight_floats(d.Cout, a.Cin, d.kD, d.kH, d.kW, 4) + 3) & ~(size_t)3;   // 16-byte aligned tail
-            return launch_f16(a, reinterpret_cast<const _Float16*>(wp + off), s);
+            return launch_f16(a, reinterpret_cast<const _Float16*>(wp + off), s, gexp);
         }
         SdcConvDesc d4 = d;
         d4.precision = 4;

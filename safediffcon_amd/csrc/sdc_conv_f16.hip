@@ -44,6 +44,7 @@ struct F16Args {
     const float* res;
     float* y;
     double* gn_part;
+    const int32_t* gexp;      // SCALED (data gradient of fine-tuning precision 6 / 7): exponent e of sdc_f16_grad_exponent
     int64_t x0s[5], x1s[5], ys[5], rs[5];
     int B, Cin0, Cin, Cout, oD, oH, W, lgW;
     int pD, kD;
@@ -58,7 +59,9 @@ struct F16Args {
 // KH = 3: 3x3 / 3x3x3 taps (9 taps per stage); KH = 1: 1x3 taps (3 taps per stage)
 // ITB: B staging items per thread; 8 (rows of 128, or planes of 1-2 rows at rows of 16: more staged rows) takes more registers
 // and LDS than two workgroups per CU leave, and runs one
-template <int KH, int ITB>
+// SCALED (sdc_conv_dgrad_f16 only): the activations -- a loss gradient -- are multiplied by 2^e before they are rounded and the
+// accumulators by 2^-e in the epilogue (both exact), e read from device memory; the samplers' instances are the unscaled ones
+template <int KH, int ITB, bool SCALED = false>
 __global__ __launch_bounds__(F16_NT) __attribute__((amdgpu_waves_per_eu(ITB > 6 ? 1 : 2))) SDC_NO_DS_MERGE void conv_f16_kernel(const F16Args a) {
     constexpr int KC = 32;
     constexpr int NTAP = 3 * KH;
@@ -75,6 +78,8 @@ __global__ __launch_bounds__(F16_NT) __attribute__((amdgpu_waves_per_eu(ITB > 6 
     const int mt = logical % a.mtiles, nt = logical / a.mtiles;
     const int m0 = mt * F16_BM, n0 = nt * F16_BN;
     const int r0 = n0 >> a.lgW;
+    float gsc = 1.0f, gunsc = 1.0f;
+    if (SCALED) { const int e = *a.gexp; gsc = __builtin_ldexpf(1.0f, e); gunsc = __builtin_ldexpf(1.0f, -e); }
 
     // ---- per-thread B staging items: (octet o, staged row sr, column w), w fastest; bases without the channel / depth-tap part
     int64_t bb0[ITB], bb1[ITB];
@@ -149,7 +154,7 @@ __global__ __launch_bounds__(F16_NT) __attribute__((amdgpu_waves_per_eu(ITB > 6 
             if (tid + k * F16_NT < a.itemsB) {
                 half8 h;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) h[i] = (_Float16)bv[k][i];          // RNE (v_cvt_pk_f16_f32)
+                for (int i = 0; i < 8; ++i) h[i] = (_Float16)(SCALED ? bv[k][i] * gsc : bv[k][i]);   // RNE (v_cvt_pk_f16_f32)
                 *reinterpret_cast<half8*>(lds + bdst[k]) = h;
             }
         }
@@ -229,7 +234,7 @@ __global__ __launch_bounds__(F16_NT) __attribute__((amdgpu_waves_per_eu(ITB > 6 
             for (int rr = 0; rr < 16; ++rr) {
                 const int co = m0 + 32 * i + 4 * lh + (rr & 3) + 8 * (rr >> 2);
                 if (pok && co < a.Cout) {
-                    float v = acc[i][j][rr] + (a.bias ? a.bias[co] : 0.0f);
+                    float v = (SCALED ? acc[i][j][rr] * gunsc : acc[i][j][rr]) + (a.bias ? a.bias[co] : 0.0f);
                     if (a.res) v = v + a.res[roff + (int64_t)co * a.rs[1]];
                     a.y[yoff + (int64_t)co * a.ys[1]] = v;
                     if (gn) { gs[i][rr >> 2] += (double)v; gq[i][rr >> 2] += (double)v * v; }
@@ -335,13 +340,13 @@ const char* f16_name(const SdcConvDesc& d) {
     return d.kD == 3 ? "conv_f16_kernel<3x3x3>" : (d.kH == 3 ? "conv_f16_kernel<3x3>" : "conv_f16_kernel<1x3>");
 }
 
-int launch_f16(const ConvArgs& c, const _Float16* wh, hipStream_t s) {
+int launch_f16(const ConvArgs& c, const _Float16* wh, hipStream_t s, const int32_t* gexp) {
     const SdcConvDesc& d = c.d;
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wh) % 16 == 0, SDC_EALIGN, "sdc_conv[fp16]: the packed weight buffer must be 16-byte aligned");
     const F16Shape sh = f16_shape(d);
     const int KC = f16_kc(d.kD, d.kH, d.kW);
     F16Args a;
-    a.x0 = c.x0; a.x1 = c.x1 ? c.x1 : c.x0; a.wh = wh; a.bias = c.bias; a.res = c.res; a.y = c.y; a.gn_part = c.gn_part;
+    a.x0 = c.x0; a.x1 = c.x1 ? c.x1 : c.x0; a.wh = wh; a.bias = c.bias; a.res = c.res; a.y = c.y; a.gn_part = c.gn_part; a.gexp = gexp;
     for (int i = 0; i < 5; ++i) { a.x0s[i] = d.x0s[i]; a.x1s[i] = d.Cin1 ? d.x1s[i] : d.x0s[i]; a.ys[i] = d.ys[i]; a.rs[i] = d.rs[i]; }
     a.B = d.B; a.Cin0 = d.Cin0; a.Cin = d.Cin0 + d.Cin1; a.Cout = d.Cout; a.oD = d.oD; a.oH = d.oH; a.W = d.oW;
     a.lgW = d.oW == 16 ? 4 : d.oW == 32 ? 5 : d.oW == 64 ? 6 : 7;
@@ -356,16 +361,22 @@ int launch_f16(const ConvArgs& c, const _Float16* wh, hipStream_t s) {
     SDC_REQUIRE((int64_t)a.ntiles * a.mtiles < (1ll << 31), SDC_EINVAL, "sdc_conv[fp16]: grid too large");
     // (the GroupNorm scratch -- 4 waves x 8 blocks x 2 doubles -- lives in the dead stage images)
     const dim3 grid((unsigned)(a.ntiles * a.mtiles));
-#define F16_LAUNCH(KH, ITB)                                                                             \
+#define F16_LAUNCH_SC(KH, ITB, SC)                                                                      \
     do {                                                                                                \
         static std::atomic<uint64_t> attr{0};                                                           \
-        SDC_LDS_OPTIN(attr, (conv_f16_kernel<KH, ITB>), 160 * 1024, "sdc_conv[fp16]");                  \
-        hipLaunchKernelGGL((conv_f16_kernel<KH, ITB>), grid, dim3(F16_NT), sh.lds, s, a);               \
+        SDC_LDS_OPTIN(attr, (conv_f16_kernel<KH, ITB, SC>), 160 * 1024, "sdc_conv[fp16]");              \
+        hipLaunchKernelGGL((conv_f16_kernel<KH, ITB, SC>), grid, dim3(F16_NT), sh.lds, s, a);           \
+    } while (0)
+#define F16_LAUNCH(KH, ITB)                                                                             \
+    do {                                                                                                \
+        if (gexp) F16_LAUNCH_SC(KH, ITB, true);                                                         \
+        else F16_LAUNCH_SC(KH, ITB, false);                                                             \
     } while (0)
     if (d.kH == 3 && sh.itemsB <= 6 * F16_NT && sh.lds <= 80u * 1024u) F16_LAUNCH(3, 6);
     else if (d.kH == 3) F16_LAUNCH(3, 8);
     else F16_LAUNCH(1, 4);             // (1-D: 4 * 256 items and < 40 KB of LDS at every row width)
 #undef F16_LAUNCH
+#undef F16_LAUNCH_SC
     return sdc::check_launch("sdc_conv[fp16]");
 }
 

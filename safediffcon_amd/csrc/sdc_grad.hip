@@ -1113,7 +1113,13 @@ struct PackArgs {
     const float* w; float* out;
     int Cout, Cin, kD, kH, kW, flip;       // logical (packed) channel counts
     int64_t n0, n1, n2, n3, n4;            // floats of the five sections (n4: F(4,3) taps of a 1-D conv, after the others)
+    int64_t nh;                            // precision 8: float offset of the fp16 tail (16-byte aligned; 0 = no tail)
 };
+
+// the tap shapes with an fp16 tail at precisions 6 / 7 / 8 (1x1x3, 1x3x3, 3x3x3; sdcconv::f16_kc)
+__host__ __device__ inline bool f16_taps(int kD, int kH, int kW) {
+    return kW == 3 && ((kD == 1 && kH == 1) || ((kD == 1 || kD == 3) && kH == 3));
+}
 
 // One workgroup stages a (co_t co) x (ci_t ci) x taps block of the weight through LDS -- read along the source's contiguous axis
 // ([co][ci, taps] rows, or [ci][co, taps] rows when flipped), written along co, the packed layouts' contiguous axis -- and emits
@@ -1222,6 +1228,21 @@ __device__ __forceinline__ void pack_weight_tile(const PackArgs& a, const int co
                 emit4(o + (((int64_t)jd * a.Cin + ci0 + ci) * a.Cout + co0 + co) * 16 + j * 4, s0, s1, s2);
             }
     }
+    if (a.nh) {                                           // precision 8: Wh[tap][ci / 32][co][ci % 32] = (fp16, RNE), Cin zero-padded
+        _Float16* o = reinterpret_cast<_Float16*>(a.out + a.nh);
+        const int nch = (a.Cin + 31) / 32;
+        const int ncz = ci0 + nci == a.Cin ? nch * 32 - ci0 : nci;     // the last channel block also writes the padding
+        for (int tap = 0; tap < taps; ++tap)
+            for (int e = threadIdx.x; e < nco * ncz; e += NT) {
+                const int ci = e % ncz, co = e / ncz, c = ci0 + ci;
+                o[(((int64_t)tap * nch + c / 32) * a.Cout + co0 + co) * 32 + c % 32] =
+                    ci < nci ? (_Float16)tile[co * pitch + ci * taps + tap] : (_Float16)0.0f;
+            }
+        if (bx == 0 && by == 0) {
+            const int64_t n4 = a.n0 + a.n1 + a.n2 + a.n3 + a.n4;
+            for (int64_t e = n4 + threadIdx.x; e < a.nh; e += NT) a.out[e] = 0.0f;           // the alignment gap
+        }
+    }
 }
 
 __global__ __launch_bounds__(NT) void pack_weight_kernel(const PackArgs a, const int co_sh, const int ci_sh, const unsigned tap_magic) {
@@ -1244,6 +1265,7 @@ __global__ __launch_bounds__(NT) void pack_weight_batch_kernel(const SdcPackItem
     PackArgs a;
     a.w = it.w; a.out = it.out; a.Cout = it.Cout; a.Cin = it.Cin; a.kD = it.kD; a.kH = it.kH; a.kW = it.kW; a.flip = it.flip;
     a.n0 = it.n[0]; a.n1 = it.n[1]; a.n2 = it.n[2]; a.n3 = it.n[3]; a.n4 = it.n[4];
+    a.nh = it.precision == 8 && f16_taps(it.kD, it.kH, it.kW) ? (a.n0 + a.n1 + a.n2 + a.n3 + a.n4 + 3) & ~(int64_t)3 : 0;
     const int r = b - it.block0;
     pack_weight_tile(a, it.co_sh, it.ci_sh, it.tap_magic, r % it.grid_x, r / it.grid_x, tile);
 }
@@ -1283,7 +1305,7 @@ extern "C" size_t sdc_pack_conv_weight_floats(int Cout, int Cin, int kD, int kH,
     int64_t n[5];
     pack_sections(Cout, Cin, kD, kH, kW, precision, n);
     const size_t n4 = (size_t)(n[0] + n[1] + n[2] + n[3] + n[4]);
-    const int kc = (precision == 6 || precision == 7) ? sdcconv::f16_kc(kD, kH, kW) : 0;
+    const int kc = (precision == 6 || precision == 7 || precision == 8) ? sdcconv::f16_kc(kD, kH, kW) : 0;
     if (!kc) return n4;
     return ((n4 + 3) & ~(size_t)3) + (size_t)kD * kH * kW * ((Cin + kc - 1) / kc) * kc * Cout / 2;
 }
@@ -1291,14 +1313,16 @@ extern "C" size_t sdc_pack_conv_weight_floats(int Cout, int Cin, int kD, int kH,
 extern "C" int sdc_pack_conv_weight(const float* w, float* out, int Cout, int Cin, int kD, int kH, int kW, int precision, int flip,
                                     void* stream) {
     SDC_REQUIRE(w && out, SDC_ENULL, "sdc_pack_conv_weight: null pointer");
-    SDC_REQUIRE(Cout > 0 && Cin > 0 && kD > 0 && kH > 0 && kW > 0 && (precision == 0 || (precision >= 2 && precision <= 7)), SDC_EINVAL,
+    SDC_REQUIRE(Cout > 0 && Cin > 0 && kD > 0 && kH > 0 && kW > 0 && (precision == 0 || (precision >= 2 && precision <= 8)), SDC_EINVAL,
                 "sdc_pack_conv_weight: bad arguments");
-    SDC_REQUIRE(precision < 6 || !flip, SDC_EINVAL, "sdc_pack_conv_weight: precisions 6 / 7 are sampler modes: no data-gradient packing");
+    SDC_REQUIRE(!(precision == 6 || precision == 7) || !flip, SDC_EINVAL,
+                "sdc_pack_conv_weight: precisions 6 / 7 are sampler layouts: no data-gradient packing (the fine-tuning layout is 8)");
     PackArgs a;
     a.w = w; a.out = out; a.Cout = Cout; a.Cin = Cin; a.kD = kD; a.kH = kH; a.kW = kW; a.flip = flip;
     int64_t n[5];
     pack_sections(Cout, Cin, kD, kH, kW, precision, n);
     a.n0 = n[0]; a.n1 = n[1]; a.n2 = n[2]; a.n3 = n[3]; a.n4 = n[4];
+    a.nh = precision == 8 && f16_taps(kD, kH, kW) ? (n[0] + n[1] + n[2] + n[3] + n[4] + 3) & ~(int64_t)3 : 0;
     int co_sh, ci_sh;
     size_t lds;
     pack_tile_shape(Cout, Cin, kD * kH * kW, co_sh, ci_sh, lds);
@@ -1326,7 +1350,8 @@ extern "C" int sdc_pack_batch_plan(SdcPackItem* items, int n, int* total_blocks,
         SdcPackItem& it = items[i];
         SDC_REQUIRE(it.w && it.out, SDC_ENULL, "sdc_pack_batch_plan: item %d: null pointer", i);
         SDC_REQUIRE(it.Cout > 0 && it.Cin > 0 && it.kD > 0 && it.kH > 0 && it.kW > 0 &&
-                    (it.precision == 0 || (it.precision >= 2 && it.precision <= 5)), SDC_EINVAL, "sdc_pack_batch_plan: item %d: bad arguments", i);
+                    (it.precision == 0 || (it.precision >= 2 && it.precision <= 5) || it.precision == 8), SDC_EINVAL,
+                    "sdc_pack_batch_plan: item %d: bad arguments (precision 0, 2 ... 5 or 8)", i);
         const int taps = it.kD * it.kH * it.kW;
         size_t lds;
         pack_tile_shape(it.Cout, it.Cin, taps, it.co_sh, it.ci_sh, lds);

@@ -117,10 +117,13 @@ def f16_kc(k):
     return 32 if tuple(k) in ((1, 1, 3), (1, 3, 3), (3, 3, 3)) else 0
 
 
-def f16_tail(t):
+def f16_tail(t, flip=False):
     """fp16 tail of a precision-6 conv weight (Cout, Cin, *k) (include/sdc.h): Wh[tap][ci // KC][co][ci % KC] = w[co][ci][tap] rounded to
-    fp16 (RNE), Cin zero-padded to whole KC chunks, returned as the float32 words that hold it"""
+    fp16 (RNE), Cin zero-padded to whole KC chunks, returned as the float32 words that hold it.  flip: the tail of the data-gradient
+    weight of a precision-8 buffer (flip = 1): channels transposed, taps flipped, then rounded"""
     t5 = as5(t).to(torch.float32)
+    if flip:
+        t5 = t5.transpose(0, 1).flip((2, 3, 4))
     co, ci = t5.shape[0], t5.shape[1]
     kc = f16_kc(t5.shape[2:])
     nch = (ci + kc - 1) // kc

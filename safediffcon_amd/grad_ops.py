@@ -22,16 +22,12 @@ def _need_cuda(*ts):
             raise RuntimeError("safediffcon_amd runs on MI355X only: tensors must be on a cuda (HIP) device; there is no CPU fallback")
 
 
-def conv_wgrad(g, x, k, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), bias=True):
-    """dw[m][n][k...] = sum_{b,pos} g[b][m][pos] x[b][n][pos*s - p + tap]   (sdc_conv_wgrad)
-    g (B, M, oD, oH, oW) and x (B, N, iD, iH, iW) are 5-D views (any strides); returns (dw (M, N, kD, kH, kW), dbias (M,) | None)."""
-    _need_cuda(g, x)
+def _wgrad_desc(g, x, k, stride, pad, up, precision):
     g, x = as5(g), as5(x)
     if tuple(k) == (1, 1, 1) and g.shape[2:] == (1, 1, 1) and x.shape[2:] == (1, 1, 1) and g.shape[0] > 1:
         # nn.Linear over a batch of rows: the batch is the position axis (16 rows per MFMA chunk instead of one)
         g = g.reshape(g.shape[0], g.shape[1]).t().reshape(1, g.shape[1], 1, 1, g.shape[0])
         x = x.reshape(x.shape[0], x.shape[1]).t().reshape(1, x.shape[1], 1, 1, x.shape[0])
-    lib = _lib.get_lib()
     d = SdcWgradDesc()
     d.B, d.M, d.N = g.shape[0], g.shape[1], x.shape[1]
     d.oD, d.oH, d.oW = g.shape[2:]
@@ -40,15 +36,57 @@ def conv_wgrad(g, x, k, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), bias=True
     d.sD, d.sH, d.sW = stride
     d.pD, d.pH, d.pW = pad
     d.uD, d.uH, d.uW = up
+    d.precision = precision
     d.gs[:] = tuple(int(s) for s in g.stride())
     d.xs[:] = tuple(int(s) for s in x.stride())
-    nbytes = int(lib.sdc_conv_wgrad_bytes(C.byref(d)))
+    return d, g, x
+
+
+def conv_wgrad(g, x, k, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), bias=True, precision=0, exp=None):
+    """dw[m][n][k...] = sum_{b,pos} g[b][m][pos] x[b][n][pos*s - p + tap]   (sdc_conv_wgrad)
+    g (B, M, oD, oH, oW) and x (B, N, iD, iH, iW) are 5-D views (any strides); returns (dw (M, N, kD, kH, kW), dbias (M,) | None).
+    precision 6 / 7 (fine-tuning with fp16 operands, sdc_conv_wgrad_f16): exp = the device exponent of g (f16_grad_exponent);
+    shapes the fp16 kernel does not take (or, at 6, its dispatch table leaves on fp32) run sdc_conv_wgrad."""
+    _need_cuda(g, x)
+    lib = _lib.get_lib()
+    f16 = precision in (6, 7)
+    if f16 and exp is None:
+        raise ValueError("conv_wgrad: precision 6 / 7 needs the exponent of g (f16_grad_exponent)")
+    d, g, x = _wgrad_desc(g, x, k, stride, pad, up, precision if f16 else 0)
+    nbytes = int(lib.sdc_conv_wgrad_f16_bytes(C.byref(d)) if f16 else lib.sdc_conv_wgrad_bytes(C.byref(d)))
     work = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=g.device)
     dw = torch.empty((d.M, d.N, *k), dtype=torch.float32, device=g.device)
     db = torch.empty(d.M, dtype=torch.float32, device=g.device) if bias else None
+    if f16:
+        check(lib.sdc_conv_wgrad_f16(C.byref(d), g.data_ptr(), x.data_ptr(), exp.data_ptr(), dw.data_ptr(),
+                                     0 if db is None else db.data_ptr(), work.data_ptr(), nbytes, _stream(g)), "sdc_conv_wgrad_f16")
+        return dw, db
     check(lib.sdc_conv_wgrad(C.byref(d), g.data_ptr(), x.data_ptr(), dw.data_ptr(), 0 if db is None else db.data_ptr(),
                              work.data_ptr(), nbytes, _stream(g)), "sdc_conv_wgrad")
     return dw, db
+
+
+def conv_wgrad_kernel(g, x, k, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), precision=0):
+    """name of the kernel conv_wgrad(..., precision) runs for these operands (sdc_conv_wgrad_describe; launches nothing)"""
+    d, _, _ = _wgrad_desc(g, x, k, stride, pad, up, precision)
+    buf = C.create_string_buffer(96)
+    check(_lib.get_lib().sdc_conv_wgrad_describe(C.byref(d), buf, 96), "sdc_conv_wgrad_describe")
+    return buf.value.decode()
+
+
+F16_EXP_INTS = 1025     # SDC_F16_EXP_INTS
+
+
+def f16_grad_exponent(g):
+    """int32 device tensor whose element 0 is the power-of-two scale exponent e of g (max|g| 2^e in [2^14, 2^15); 0 when max|g| is 0
+    or not finite): sdc_f16_grad_exponent, on the current stream, no host sync"""
+    _need_cuda(g)
+    g5 = as5(g)
+    e = torch.empty(F16_EXP_INTS, dtype=torch.int32, device=g.device)
+    st = (C.c_int64 * 5)(*(int(s) for s in g5.stride()))
+    check(_lib.get_lib().sdc_f16_grad_exponent(g5.data_ptr(), *(int(v) for v in g5.shape), C.addressof(st), e.data_ptr(), _stream(g)),
+          "sdc_f16_grad_exponent")
+    return e
 
 
 def gn_stats(h, groups, eps=1e-5):

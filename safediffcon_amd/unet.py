@@ -298,6 +298,14 @@ class _HipUNet(nn.Module):
         # operands, fp32 accumulation; ~5e-7 eps-MSE; 7 = the same on every covered conv, a test hook); forward_train and the
         # differentiable paths keep precision 4.  Set before the first call of a shape (plans are cached per precision).
         self.precision = 4
+        # fine-tuning precision (forward_train: p_losses, GraphedLossStep, the differentiable last DDIM step), read at every
+        # forward_train: None (default) = the fp32 kernels of `precision` above, bit for bit; 6 (opt-in) = the stride-1 pad-1 3-tap
+        # convs (1x1x3 / 1x3x3 / 3x3x3) with fp16 operands and fp32 accumulation in all three directions -- forward, data gradient,
+        # weight gradient (per-tensor power-of-two scale of the loss gradient, computed on the device) -- where measured faster,
+        # the reference's fp16 mixed-precision fine-tuning; 7 = the same on every covered conv (test hook).  Everything else (1x1,
+        # strided, upsampling, stem convs, attention, linear layers, norms) stays fp32.  No effect on net(x, t) or the samplers; a
+        # live GraphedLossStep keeps the mode it was captured with.  Other values raise ValueError.
+        self.train_precision = None
         # LinearAttention blocks of width 64 / 128 as the fused 3-launch form (csrc/sdc_lablock.hip); False = the
         # unfused chain norm -> 1x1 -> attention core -> 1x1 -> norm (kept for wider layers and for A/B checks)
         self.fuse_linattn = True
@@ -329,6 +337,15 @@ class _HipUNet(nn.Module):
                 self.cond_offsets[k[: -len(".mlp.1.weight")]] = off
                 off += shape[0]
         self.cond_width = off
+
+    @property
+    def train_precision(self):
+        return self.__dict__.get("_train_precision")
+
+    @train_precision.setter
+    def train_precision(self, v):
+        from .autograd import check_train_precision
+        self.__dict__["_train_precision"] = check_train_precision(v)
 
     def P(self, key):
         m = self

@@ -31,8 +31,8 @@ import torch
 from torch.autograd import Function
 
 from . import _lib, grad_ops
-from ._lib import SdcConvDesc, check
-from .engine import as5, pack_conv_weight
+from ._lib import check
+from .engine import as5, conv_desc, conv_precision, pack_conv_weight
 
 HEADS, DIM_HEAD = 4, 32
 HID = HEADS * DIM_HEAD
@@ -62,32 +62,8 @@ def conv_raw(x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), 
     if out is None:
         out = torch.empty((B, cout, *(osz(i, u, kk, s, p) for i, u, kk, s, p in zip((iD, iH, iW), up, k, stride, pad))),
                           dtype=torch.float32, device=x.device)
-    nw = k[0] * k[1] * k[2] * (c0 + c1) * cout
-    n = wp.numel()
-    if prec is not None:
-        assert prec in (6, 7) and n == int(lib.sdc_pack_conv_weight_floats(cout, c0 + c1, *k, 8)), (prec, n, k, c0, c1, cout)
-    elif k[2] == 3 and n != nw:
-        prec = 0
-        prec = 2 if n == nw + nw // 3 * 4 else (3 if n == nw + nw // 3 * 4 + nw // 9 * 16 else 4)
-        if tuple(k) == (1, 1, 3) and n == nw + nw // 3 * 4 + nw // 3 * 6:
-            prec = 5                                                     # 1-D conv packed with its F(4,3) taps
-        assert prec != 4 or n == nw + nw // 3 * 4 + nw // 9 * 16 + nw // 27 * 64, (n, nw)
-    else:
-        prec = 0
-        assert n == nw, (n, nw, k, c0, c1, cout)
-    d = SdcConvDesc()
-    d.B, d.Cin0, d.Cin1, d.Cout = B, c0, c1, cout
-    d.iD, d.iH, d.iW = iD, iH, iW
-    d.oD, d.oH, d.oW = out.shape[2:]
-    d.kD, d.kH, d.kW = k
-    d.sD, d.sH, d.sW = stride
-    d.pD, d.pH, d.pW = pad
-    d.uD, d.uH, d.uW = up
-    d.up_mode, d.precision = up_mode, prec
-    d.x0s[:] = tuple(int(s) for s in x.stride())
-    d.x1s[:] = tuple(int(s) for s in x1.stride()) if x1 is not None else (0,) * 5
-    d.ys[:] = tuple(int(s) for s in out.stride())
-    d.rs[:] = tuple(int(s) for s in residual.stride()) if residual is not None else (0,) * 5
+    prec = conv_precision(wp.numel(), k, c0 + c1, cout, f16=prec, train=prec is not None)
+    d = conv_desc(x, x1, out, residual, cout, k, stride, pad, up, up_mode, prec)
     p = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
     split_wins = prec == 6 and SPLIT_SMALL_GRIDS and residual is None and not getattr(_BATCH_INVARIANT, "on", False) \
         and int(lib.sdc_conv_splitk_bytes(C.byref(d))) > 0

@@ -8,8 +8,9 @@
 namespace sdcconv {
 
 
-// Dispatch overrides and tuning knobs (SDC_NO_WG2, SDC_TILE, ...) exist only in experiment builds (-DSDC_KERNEL_EXPERIMENTS,
-// tools/): the shipping library reads no environment variable; the conv algorithm is chosen by SdcConvDesc.precision alone.
+// The result-changing debug modes of the Winograd kernels (SDC_WG2_DBG, SDC_WG3_DBG, SDC_WG3S_DBG) exist only in experiment builds
+// (-DSDC_KERNEL_EXPERIMENTS, tools/): the shipping library reads no environment variable; the conv algorithm is chosen by
+// SdcConvDesc.precision alone.
 #ifdef SDC_KERNEL_EXPERIMENTS
 inline int exp_env(const char* name) { const char* v = getenv(name); return v ? atoi(v) : 0; }
 #else
@@ -51,7 +52,6 @@ struct ConvArgs {
     int Ktot;      // taps*Cin
     int Cin;
     int lgD, lgH, lgW;
-    int rowhalo;   // allow the row-halo kernel (env SDC_NO_ROWHALO=1 disables it for A/B timing)
     int vec2;      // Winograd epilogue: y (and residual) rows allow 8-byte accesses at even positions
     int ydense;    // y (and the residual) dense per sample and below 2^30 elements: conv_epilogue addresses them as scalar channel base + 32-bit lane offset
     const float* wg2;   // F(2x2,3x3) taps [kd][Cin][Cout][16] (precision 3) / F(2x2x2,3x3x3) taps [jd][Cin][Cout][16] (precision 4)
@@ -83,13 +83,13 @@ inline int64_t span5(const int64_t* st, int b, int c, int dd, int h, int w) {
 }
 
 // defined in sdc_conv_wino.hip
-bool wg2_ok(const SdcConvDesc& d, bool small, bool rowhalo);
-bool wg3_ok(const SdcConvDesc& d, bool small, bool rowhalo);
+bool wg2_ok(const SdcConvDesc& d, bool small);
+bool wg3_ok(const SdcConvDesc& d, bool small);
 int launch_wg2(const ConvArgs& a, hipStream_t s);
 int wg2_ksplit(const SdcConvDesc& d);         // Cin split sdc_conv_splitk would use for this conv (1: none)
 int launch_wg3(const ConvArgs& a, hipStream_t s);
-bool wg3s_ok(const SdcConvDesc& d, bool small, bool rowhalo);
-bool wg2s_ok(const SdcConvDesc& d, bool small, bool rowhalo);
+bool wg3s_ok(const SdcConvDesc& d, bool small);
+bool wg2s_ok(const SdcConvDesc& d, bool small);
 int launch_wg2s(const ConvArgs& a, hipStream_t s);
 int launch_wg3s(const ConvArgs& a, hipStream_t s);
 

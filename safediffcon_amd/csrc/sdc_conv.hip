@@ -15,6 +15,7 @@
 // global loads for chunk c+1 are issued before the MFMAs of chunk c and written to the other LDS
 // buffer afterwards (one barrier per chunk).
 #include "sdc_conv.h"
+#include <string>
 
 using namespace sdcconv;
 
@@ -491,7 +492,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3))) void co
 
 template <int BM, int BN, int WM, int WN>
 void launch_pw(const ConvArgs& a, hipStream_t s) {
-    dim3 grid(((a.Ntot + BN - 1) / BN) * ((a.d.Cout + BM - 1) / BM));
+    dim3 grid(((a.Ntot + BN - 1) / BN) * ((a.d.Cout + BM - 1) / BM), a.ksplit);
     hipLaunchKernelGGL((conv_pw_kernel<BM, BN, WM, WN>), grid, dim3(NT), 0, s, a);
 }
 
@@ -1571,18 +1572,6 @@ int launch_wg(const ConvArgs& a, hipStream_t s) {
     return SDC_OK;
 }
 
-// what the dispatch chose for the last descriptor (sdc_conv_describe): kernel template instance and the share of the
-// direct-form multiply-adds it issues on the matrix cores (Winograd forms issue fewer)
-thread_local const char* tl_pick = "";
-thread_local double tl_factor = 1.0;
-thread_local bool tl_describe = false;
-#define SDC_PICK(nm, f)                      \
-    do {                                     \
-        tl_pick = (nm);                      \
-        tl_factor = (f);                     \
-        if (tl_describe) return SDC_OK;      \
-    } while (0)
-
 int ilog2_pow2(int v) {
     int l = 0;
     while ((1 << l) < v) ++l;
@@ -1596,41 +1585,37 @@ int ilog2_exact(int v) {
     return -1;
 }
 
-template <int BM, int BN, int WM, int WN>
-int launch(const ConvArgs& a, bool fast, hipStream_t s, const char* n_rh, const char* n_fast, const char* n_gen) {
-    dim3 grid((a.Ntot + BN - 1) / BN, (a.d.Cout + BM - 1) / BM);
-    const SdcConvDesc& d = a.d;
-    // row-halo kernel: stride 1 along W, no virtual upsampling, kW == 3 (with kW == 1 there is no halo to share and
-    // the plain kernel measured faster), whole rows or whole row segments per tile
-    const bool rh = fast && a.rowhalo && d.sW == 1 && d.uD == 1 && d.uH == 1 && d.uW == 1 && d.up_mode == 0 &&
-                    d.kW == 3 && d.kD * d.kH <= 32 && d.Cout % 4 == 0 &&
-                    ((d.oW % BN == 0) || (BN % d.oW == 0 && d.oW >= 16)) &&
-                    (reinterpret_cast<uintptr_t>(a.wp) % 16 == 0);
-    if constexpr (BM >= 64) {
-        if (rh) { SDC_PICK(n_rh, 1.0); hipLaunchKernelGGL((conv_rh_kernel<BM, BN, WM, WN, 3, false>), grid, dim3(NT), 0, s, a); return SDC_OK; }
-    }
-    if (fast) {
-        SDC_PICK(n_fast, 1.0);
-        hipLaunchKernelGGL((conv_kernel<BM, BN, WM, WN, true>), grid, dim3(NT), 0, s, a);
-    } else {
-        SDC_PICK(n_gen, 1.0);
-        hipLaunchKernelGGL((conv_kernel<BM, BN, WM, WN, false>), grid, dim3(NT), 0, s, a);
-    }
-    return SDC_OK;
-}
-#define SDC_LAUNCH(BM, BN, WM, WN)                                                                      \
-    launch<BM, BN, WM, WN>(a, fast, s, "conv_rh_kernel<" #BM "," #BN "," #WM "," #WN ",3,false>",        \
-                           "conv_kernel<" #BM "," #BN "," #WM "," #WN ",true>", "conv_kernel<" #BM "," #BN "," #WM "," #WN ",false>")
+// Direct-form tiles (conv_kernel, conv_rh_kernel): BM x BN outputs per workgroup on WM x WN waves; blockIdx.z: the K splits of
+// sdc_conv_splitk (FAST only)
+enum class Direct { RH, FAST, GEN };      // row-halo kernel / whole K chunks per tap / general gather
+struct DirectTile { int bm, bn; const char* names[3]; };     // names: by Direct
+const DirectTile DIRECT_TILES[] = {
+    {128, 128, {"conv_rh_kernel<128,128,2,2,3,false>", "conv_kernel<128,128,2,2,true>", "conv_kernel<128,128,2,2,false>"}},
+    {64, 256, {"conv_rh_kernel<64,256,1,4,3,false>", "conv_kernel<64,256,1,4,true>", "conv_kernel<64,256,1,4,false>"}},
+    {64, 128, {"conv_rh_kernel<64,128,2,2,3,false>", "conv_kernel<64,128,2,2,true>", "conv_kernel<64,128,2,2,false>"}},
+    {64, 64, {"conv_rh_kernel<64,64,2,2,3,false>", "conv_kernel<64,64,2,2,true>", "conv_kernel<64,64,2,2,false>"}},
+    {32, 128, {nullptr, "conv_kernel<32,128,1,4,true>", "conv_kernel<32,128,1,4,false>"}},
+};
 
-// Winograd (precision 2) coverage and tile choice, shared by the dispatch and by sdc_conv_gnparts.
+template <int BM, int BN, int WM, int WN>
+void launch_direct(const ConvArgs& a, Direct form, hipStream_t s) {
+    dim3 grid((a.Ntot + BN - 1) / BN, (a.d.Cout + BM - 1) / BM, a.ksplit);
+    if constexpr (BM >= 64) {
+        if (form == Direct::RH) { hipLaunchKernelGGL((conv_rh_kernel<BM, BN, WM, WN, 3, false>), grid, dim3(NT), 0, s, a); return; }
+    }
+    if (form == Direct::FAST) hipLaunchKernelGGL((conv_kernel<BM, BN, WM, WN, true>), grid, dim3(NT), 0, s, a);
+    else hipLaunchKernelGGL((conv_kernel<BM, BN, WM, WN, false>), grid, dim3(NT), 0, s, a);
+}
+
+// Winograd (precision 2) coverage and tile choice.
 // 8-wave workgroups (two waves per SIMD) share one staged weight tile; the bigger the tile the fewer L2->LDS bytes
 // per MFMA: 128 x 256 / 128 x 128 outputs for wide layers, 64 x 512 / 64 x 256 for Cout <= 64, 4-wave 64 x 128 for
-// small grids.  pick: 3 = 64x128, 6 = 128x128, 7 = 64x256, 9 = 128x256, 10 = 64x512; 0 = not covered.
+// small grids.  pick: 3 = 64x128, 6 = 128x128, 7 = 64x256, 9 = 128x256, 10 = 64x512, 13 = 128x128 F(4,3); 0 = not covered.
 struct WgPick { int pick, bm, bn; bool ups; };
-WgPick wg_pick(const SdcConvDesc& d, int64_t ntot, bool small, bool rowhalo) {
+WgPick wg_pick(const SdcConvDesc& d, int64_t ntot, bool small) {
     WgPick w{0, 0, 0, false};
     w.ups = (d.uH > 1 || d.uW > 1);      // nearest x2 upsampling folded into the gather: one input, kD = 1, kH <= 3
-    if (!(d.precision >= 2 && rowhalo && d.kW == 3 && d.sW == 1 && d.uD == 1 && d.up_mode == 0 &&
+    if (!(d.precision >= 2 && d.kW == 3 && d.sW == 1 && d.uD == 1 && d.up_mode == 0 &&
           (!w.ups || (d.uH <= 2 && d.uW <= 2 && d.kD == 1 && d.kH <= 3 && d.sH == 1 && d.Cin1 == 0)) &&
           d.kD * d.kH <= 32 && d.Cin0 % 16 == 0 && d.Cin1 % 16 == 0 && small && d.Cout % 4 == 0 && d.Cout > 32 &&
           d.oW % 2 == 0 && d.oW >= 16 && ((int64_t)d.kD * d.kH * d.kW * (d.Cin0 + d.Cin1) * d.Cout) % 4 == 0))
@@ -1638,39 +1623,30 @@ WgPick wg_pick(const SdcConvDesc& d, int64_t ntot, bool small, bool rowhalo) {
     auto fits = [&](int bn) { return (d.oW % bn == 0) || (bn % d.oW == 0); };
     if (!fits(128)) return w;
     auto nblk = [&](int bm, int bn) { return ((ntot + bn - 1) / bn) * ((d.Cout + bm - 1) / bm); };
-    static const int wg_tile = exp_env("SDC_WG_TILE");   // tuning knob
-    int pick = wg_tile;
-    if (w.ups) {
-        pick = (d.Cout > 64 && nblk(128, 128) >= 256) ? 6 : ((d.Cout <= 64 && fits(256) && nblk(64, 256) >= 256) ? 7 : 3);
-    } else {
-        if (!pick) {
-            if (d.Cout > 64) pick = (fits(256) && nblk(128, 256) >= 256) ? 9 : (nblk(128, 128) >= 256 ? 6 : 3);
-            else pick = (fits(512) && nblk(64, 512) >= 512) ? 10 : (fits(256) && nblk(64, 256) >= 256 ? 7 : 3);
-        }
-        if ((pick == 7 || pick == 9) && !fits(256)) pick = 3;
-        if (pick == 10 && !fits(512)) pick = 3;
-        if (pick != 6 && pick != 7 && pick != 9 && pick != 10) pick = 3;
-    }
+    int pick;
+    if (w.ups) pick = (d.Cout > 64 && nblk(128, 128) >= 256) ? 6 : ((d.Cout <= 64 && fits(256) && nblk(64, 256) >= 256) ? 7 : 3);
+    else if (d.Cout > 64) pick = (fits(256) && nblk(128, 256) >= 256) ? 9 : (nblk(128, 128) >= 256 ? 6 : 3);
+    else pick = (fits(512) && nblk(64, 512) >= 512) ? 10 : (fits(256) && nblk(64, 256) >= 256 ? 7 : 3);
     // precision 5 (opt-in): 1-D convs (kD = kH = 1, one row per sample and channel) whose rows are whole quads take F(4,3), half of
     // the direct form's MFMAs instead of two thirds; 128 x 128 outputs per workgroup (the C3 layers are ~256 such tiles each).
     // NOT the default: measured at C3 the six-product kernel issues 74 TFLOP/s where the F(2,3) one
     // issues 97 -- twelve transform operations per six MFMAs are not hidden behind them -- 6.09 ms against 5.99 ms for the 33
     // layers, at three times the rounding error
-    static const int no_f43 = exp_env("SDC_NO_F43");
-    if (!no_f43 && d.precision == 5 && !w.ups && d.kD == 1 && d.kH == 1 && d.oD == 1 && d.oH == 1 && d.oW % 4 == 0 && d.Cout >= 128) pick = 13;
+    if (d.precision == 5 && !w.ups && d.kD == 1 && d.kH == 1 && d.oD == 1 && d.oH == 1 && d.oW % 4 == 0 && d.Cout >= 128) pick = 13;
     w.pick = pick;
     w.bm = (pick == 6 || pick == 9 || pick == 13) ? 128 : 64;
     w.bn = (pick == 3 || pick == 6 || pick == 13) ? 128 : (pick == 10 ? 512 : 256);
     return w;
 }
 
-// GroupNorm partial sums in the Winograd epilogue: pairs per (sample, group), 0 if the tile grid does not line up
-int gn_parts_for(const SdcConvDesc& d, const WgPick& w, int G) {
-    if (!w.pick || G <= 0 || d.Cout % G) return 0;
+// GroupNorm partial sums in a Winograd epilogue with bm x bn output tiles: pairs per (sample, group), 0 if the tile grid does not
+// line up
+int gn_parts_for(const SdcConvDesc& d, int bm, int bn, int G) {
+    if (G <= 0 || d.Cout % G) return 0;
     const int cpg = d.Cout / G;
     const int64_t S = (int64_t)d.oD * d.oH * d.oW;
-    if (cpg % 8 || S % w.bn || !(cpg % w.bm == 0 || w.bm % cpg == 0)) return 0;
-    return (int)(S / w.bn) * (cpg >= w.bm ? cpg / w.bm : 1);
+    if (cpg % 8 || S % bn || !(cpg % bm == 0 || bm % cpg == 0)) return 0;
+    return (int)(S / bn) * (cpg >= bm ? cpg / bm : 1);
 }
 
 // Cin split of sdc_conv_splitk on the 1-D F(2,3) form (conv_wg_kernel<64,128,...,ks2> on its single-tap-row path): as wg2_ksplit --
@@ -1706,6 +1682,164 @@ bool conv_small(const SdcConvDesc& d) {
     return span(d.x0s, d.B, d.iD, d.iH, d.iW) < (1ll << 30) && (d.Cin1 == 0 || span(d.x1s, d.B, d.iD, d.iH, d.iW) < (1ll << 30));
 }
 
+// y (and the residual) dense per sample and below 2^30 elements: conv_epilogue addresses them as scalar channel base + 32-bit lane offset
+bool y_dense(const SdcConvDesc& d, bool residual) {
+    auto dense = [&](const int64_t* st) { return st[4] == 1 && st[3] == d.oW && st[2] == (int64_t)d.oH * d.oW; };
+    const int64_t S = (int64_t)d.oD * d.oH * d.oW;
+    return dense(d.ys) && S >= 128 && S < (1 << 24) && span5(d.ys, d.B, d.Cout, d.oD, d.oH, d.oW) < (1ll << 30) &&
+           (!residual || (dense(d.rs) && span5(d.rs, d.B, d.Cout, d.oD, d.oH, d.oW) < (1ll << 30)));
+}
+
+// What a conv's kernel depends on besides its descriptor: the alignment of its operands and whether a residual is fused.
+// CANONICAL is what the descriptor-only queries assume: 16-byte aligned pointers (never dereferenced), no residual.
+struct Operands { const void *x0, *x1, *wp, *y, *res; };
+const void* const ALIGNED = reinterpret_cast<const void*>(uintptr_t(256));
+const Operands CANONICAL{ALIGNED, ALIGNED, ALIGNED, ALIGNED, nullptr};
+
+bool aligned(const void* p, int bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
+
+// The Winograd kernels' operands: 16-byte loads of wp, x0 (and x1); with `stores` (the two-plane and two-workgroups-per-CU
+// forms) also 8-byte stores of y and no fused residual
+bool wino_aligned(const SdcConvDesc& d, const Operands& op, bool stores) {
+    return aligned(op.wp, 16) && aligned(op.x0, 16) && (d.Cin1 == 0 || aligned(op.x1, 16)) && (!stores || (aligned(op.y, 8) && !op.res));
+}
+
+// ... and, for sdc_conv_gn's error message, which of them `op` misses
+std::string wino_misfit(const SdcConvDesc& d, const Operands& op) {
+    std::string s;
+    auto add = [&](bool miss, const char* what) { if (miss) s += (s.empty() ? "" : ", ") + std::string(what); };
+    add(!aligned(op.wp, 16), "wp is not 16-byte aligned");
+    add(!aligned(op.x0, 16), "x0 is not 16-byte aligned");
+    add(d.Cin1 > 0 && !aligned(op.x1, 16), "x1 is not 16-byte aligned");
+    add(!aligned(op.y, 8), "y is not 8-byte aligned");
+    add(op.res != nullptr, "a residual is fused");
+    return s.empty() ? "the operands differ from the descriptor-only assumption" : s;
+}
+
+// The kernel a conv runs, as route() picks it
+enum class Kern { F16, WG3S, WG3, WG2S, WG2, WG1, PW2, PW, STEM, DIRECT };
+struct Route {
+    Kern kern;
+    const char* name;     // kernel template instance (sdc_conv_describe)
+    double share;         // share of the direct form's multiply-adds it issues on the matrix cores (Winograd forms issue fewer)
+    int gn_parts;         // GroupNorm partial sums per (sample, group) its epilogue writes for the G asked for (0: none)
+    int ksplit;           // sdc_conv_splitk: workgroups per output tile, each over a share of K (1: no split)
+    bool sum_bias;        // ksplit > 1: splitk_sum_kernel adds the bias (the partial kernel then adds none)
+    int tile;             // WG1: the wg_pick code; PW2, PW, DIRECT: index into their tile lists
+    bool ups;             // WG1: the upsampling gather
+    Direct form;          // DIRECT
+};
+
+Route make_route(Kern k, const char* name, double share, int gn_parts = 0, int tile = 0) {
+    return Route{k, name, share, gn_parts, 1, false, tile, false, Direct::GEN};
+}
+
+// The one place that decides which kernel a conv runs: sdc_conv, sdc_conv_gn, sdc_conv_splitk and sdc_conv_dgrad_f16 (conv_impl,
+// with the real operands) and the descriptor-only queries sdc_conv_describe, sdc_conv_gnparts and sdc_conv_splitk_bytes (with
+// CANONICAL).  G > 0: the GroupNorm group count of sdc_conv_gn; split: sdc_conv_splitk.  Launches nothing, reads no memory.
+Route route(const SdcConvDesc& d, const Operands& op, int G, bool split) {
+    // precision 6 / 7: fp16 operands, fp32 accumulation (sdc_conv_f16.hip) for the covered 3-tap convs (6: those of the measured
+    // dispatch table); the other convs, and sdc_conv_splitk, run precision 4's kernels on the buffer's precision-4 prefix
+    if (d.precision == 6 || d.precision == 7) {
+        if (!split && f16_ok(d)) return make_route(Kern::F16, f16_name(d), 1.0, f16_gnparts(d, G));
+        SdcConvDesc d4 = d;
+        d4.precision = 4;
+        return route(d4, op, G, split);
+    }
+    const bool small = conv_small(d);
+    const int64_t ntot = (int64_t)d.B * d.oD * d.oH * d.oW;
+    const bool splits = split && !op.res;
+    // fp32 Winograd F(2x2x2,3x3x3), two workgroups per CU (round 5): 3x3x3 stride-1 convs over whole rows, plane pairs
+    if (wg3s_ok(d, small) && wino_aligned(d, op, true))
+        return make_route(Kern::WG3S, d.oW == 16 ? "conv_wg3s_kernel<16>" : (d.oW == 32 ? "conv_wg3s_kernel<32>" : "conv_wg3s_kernel<64>"),
+                          8.0 / 27.0, gn_parts_for(d, W2_BM, W3S_TILES * 8, G));
+    // fp32 Winograd F(2x2x2,3x3x3), one workgroup per CU: the shapes the form above does not take
+    if (wg3_ok(d, small) && wino_aligned(d, op, true))
+        return make_route(Kern::WG3, d.oW == 16 ? "conv_wg3_kernel<16>" : (d.oW == 32 ? "conv_wg3_kernel<32>" : "conv_wg3_kernel<64>"),
+                          8.0 / 27.0, gn_parts_for(d, W2_BM, W2_TILES * 8, G));
+    // fp32 Winograd F(2x2,3x3), two workgroups per CU (round 6): 3x3 convs (kD = 1) over whole rows of 128 / 64 / 32 -- unless
+    // sdc_conv_splitk wants to split this conv (small grids keep the one-workgroup form and its Cin split)
+    if (wg2s_ok(d, small) && wino_aligned(d, op, true) && !(split && wg2_ksplit(d) > 1))
+        return make_route(Kern::WG2S, d.oW == 128 ? "conv_wg2s_kernel<128>" : (d.oW == 64 ? "conv_wg2s_kernel<64>" : "conv_wg2s_kernel<32>"),
+                          4.0 / 9.0, gn_parts_for(d, W2_BM, W3S_TILES * 4, G));
+    // fp32 Winograd F(2x2,3x3) over (H, W): 3x3 / 3x3x3 stride-1 convs over whole rows; sdc_conv_splitk: Cin split, the bias added
+    // by the partial kernel
+    if (wg2_ok(d, small) && wino_aligned(d, op, false)) {
+        Route r = make_route(Kern::WG2, d.oW == 16 ? "conv_wg2_kernel<16>" : (d.oW == 32 ? "conv_wg2_kernel<32>" :
+                                        (d.oW == 64 ? "conv_wg2_kernel<64>" : "conv_wg2_kernel<128>")), 4.0 / 9.0,
+                             gn_parts_for(d, W2_BM, W2_TILES * 4, G));
+        r.ksplit = splits ? wg2_ksplit(d) : 1;
+        return r;
+    }
+    // fp32 Winograd F(2,3) along W: 3-wide stride-1 taps, whole 16-channel chunks, even rows; sdc_conv_splitk: Cin split on the
+    // 64 x 128 tile, the bias added by splitk_sum_kernel
+    const WgPick w = wg_pick(d, ntot, small);
+    if (w.pick && aligned(op.wp, 16)) {
+        const char* name;
+        if (w.ups) name = w.pick == 6 ? "conv_wg_kernel<128,128,4,2,16,512,ups>" : (w.pick == 7 ? "conv_wg_kernel<64,256,2,4,16,512,ups>" :
+                                                                                     "conv_wg_kernel<64,128,2,2,16,256,ups>");
+        else name = w.pick == 13 ? "conv_f43_kernel<128,128,4,16,F43>" : w.pick == 6 ? "conv_wg_kernel<128,128,4,2,16,512>" :
+                    w.pick == 7 ? "conv_wg_kernel<64,256,2,4,16,512>" : w.pick == 9 ? "conv_wg_kernel<128,256,4,2,16,512>" :
+                    w.pick == 10 ? "conv_wg_kernel<64,512,1,8,16,512>" : "conv_wg_kernel<64,128,2,2,16,512,ks2>";
+        Route r = make_route(Kern::WG1, name, w.pick == 13 ? 0.5 : 2.0 / 3.0, gn_parts_for(d, w.bm, w.bn, G), w.pick);
+        r.ups = w.ups;
+        r.ksplit = (splits && d.oW % 4 == 0 && d.ys[4] == 1) ? wg1_ksplit(d, w, ntot) : 1;
+        r.sum_bias = true;
+        return r;
+    }
+    // the direct forms (no fused GroupNorm statistics).  FAST: whole K chunks share a tap, and every per-thread offset fits the
+    // 32-bit voffset of the saddr load form
+    const bool fast = (d.Cin0 % BK == 0) && (d.Cin1 % BK == 0) && small && d.Cout < (1 << 30);
+    auto direct = [&](int t) {
+        const DirectTile& T = DIRECT_TILES[t];
+        // row-halo kernel: stride 1 along W, no virtual upsampling, kW == 3 (with kW == 1 there is no halo to share and
+        // the plain kernel measured faster), whole rows or whole row segments per tile
+        const bool rh = T.bm >= 64 && fast && d.sW == 1 && d.uD == 1 && d.uH == 1 && d.uW == 1 && d.up_mode == 0 &&
+                        d.kW == 3 && d.kD * d.kH <= 32 && d.Cout % 4 == 0 &&
+                        ((d.oW % T.bn == 0) || (T.bn % d.oW == 0 && d.oW >= 16)) && aligned(op.wp, 16);
+        Route r = make_route(Kern::DIRECT, nullptr, 1.0, 0, t);
+        r.form = rh ? Direct::RH : (fast ? Direct::FAST : Direct::GEN);
+        r.name = T.names[(int)r.form];
+        return r;
+    };
+    // pointwise convs over a dense layout: 16-byte loads of weights and activations
+    auto dense_in = [&](const int64_t* st) { return st[4] == 1 && st[3] == d.iW && st[2] == (int64_t)d.iH * d.iW && st[0] % 4 == 0 && st[1] % 4 == 0; };
+    const bool pw = fast && d.kD * d.kH * d.kW == 1 && d.sD == 1 && d.sH == 1 && d.sW == 1 && d.uD == 1 && d.uH == 1 &&
+        d.uW == 1 && d.up_mode == 0 && d.pD == 0 && d.pH == 0 && d.pW == 0 && d.oD == d.iD && d.oH == d.iH && d.oW == d.iW &&
+        (int64_t)d.oD * d.oH * d.oW % 4 == 0 && d.Cout % 4 == 0 && d.Cout > 32 && dense_in(d.x0s) && (d.Cin1 == 0 || dense_in(d.x1s)) &&
+        aligned(op.x0, 16) && (d.Cin1 == 0 || aligned(op.x1, 16)) && aligned(op.wp, 16);
+    // sdc_conv_splitk on the direct-form kernels' smallest tile: K split, the bias added by splitk_sum_kernel
+    const int sd = (splits && d.oW % 4 == 0 && d.precision != 5) ? direct_ksplit(d, ntot, fast) : 1;
+    if (sd > 1) {
+        Route r = pw ? make_route(Kern::PW, "conv_pw_kernel<64,64,2,2>", 1.0, 0, 3) : direct(3);
+        r.ksplit = sd;
+        r.sum_bias = true;
+        return r;
+    }
+    if (pw) {
+        // two-workgroups-per-CU form with interleaved tiles (round 5): whole 128-channel blocks, 16-byte aligned dense rows of y
+        // (and of the residual), enough 128 x 256 tiles for two rounds of the chip
+        const bool al16 = aligned(op.y, 16) && d.ys[0] % 4 == 0 && d.ys[1] % 4 == 0 &&
+                          (!op.res || (aligned(op.res, 16) && d.rs[0] % 4 == 0 && d.rs[1] % 4 == 0));
+        const bool pw2 = al16 && y_dense(d, op.res != nullptr);
+        if (pw2 && d.Cout % 128 == 0 && ((ntot + 255) / 256) * (d.Cout / 128) >= 1024) return make_route(Kern::PW2, "conv_pw2_kernel<2,2>", 1.0, 0, 0);
+        if (pw2 && d.Cout == 64 && (ntot + 511) / 512 >= 1024) return make_route(Kern::PW2, "conv_pw2_kernel<1,4>", 1.0, 0, 1);
+        if (d.Cout > 64 && ntot >= 128 * 256) return make_route(Kern::PW, "conv_pw_kernel<128,128,2,2>", 1.0, 0, 0);
+        if (d.Cout <= 64 && ntot >= 256 * 1024) return make_route(Kern::PW, "conv_pw_kernel<64,256,1,4>", 1.0, 0, 1);
+        if (((ntot + 127) / 128) * ((d.Cout + 63) / 64) >= 1024) return make_route(Kern::PW, "conv_pw_kernel<64,128,2,2>", 1.0, 0, 2);
+        return make_route(Kern::PW, "conv_pw_kernel<64,64,2,2>", 1.0, 0, 3);
+    }
+    // stem convs (kW = 7, tiny Cin): row-halo kernel with generalized k rows
+    if (d.kW == 7 && d.sW == 1 && d.uD == 1 && d.uH == 1 && d.uW == 1 && d.up_mode == 0 && d.kD * d.kH <= 64 &&
+        d.Cout % 4 == 0 && d.Cout > 32 && small && ((d.oW % 128 == 0) || (128 % d.oW == 0 && d.oW >= 16)) && aligned(op.wp, 16))
+        return make_route(Kern::STEM, "conv_rh_kernel<64,128,2,2,7,true>", 1.0);
+    if (d.Cout > 64 && ntot >= 128 * 256) return direct(0);
+    if (d.Cout > 32 && d.Cout <= 64 && ntot >= 256 * 1024) return direct(1);     // wide tile: each wave owns 64x64 (2x2 MFMA tiles) like the 128x128 case
+    if (d.Cout > 32 && ((ntot + 127) / 128) * ((d.Cout + 63) / 64) >= 1024) return direct(2);
+    if (d.Cout > 32) return direct(3);                                           // small-N layers: twice the workgroups, >= 2 per CU
+    return direct(4);
+}
+
 // y (strided) = sum over the splits, in split order, of the dense partial copies of sdc_conv_splitk
 __global__ __launch_bounds__(256) void splitk_sum_kernel(const float* __restrict__ part, float* __restrict__ y, int S, int64_t elems, int C,
                                                          int oD, int oH, int oW, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
@@ -1724,6 +1858,29 @@ __global__ __launch_bounds__(256) void splitk_sum_kernel(const float* __restrict
     if (bias) acc += bias[c];                    // (the 1-D form: its splits carry no bias)
     float* o = y + b * s0 + c * s1 + dd * s2 + h * s3 + w * s4;
     o[0] = acc.x; o[s4] = acc.y; o[2 * s4] = acc.z; o[3 * s4] = acc.w;
+}
+
+// the checks of a descriptor and its operands every conv entry point makes (sdc_conv_describe: with CANONICAL)
+int check_conv(const SdcConvDesc& d, const Operands& op, bool gn) {
+    SDC_REQUIRE(d.B > 0 && d.Cin0 > 0 && d.Cin1 >= 0 && d.Cout > 0, SDC_EINVAL, "sdc_conv: bad channel/batch counts");
+    SDC_REQUIRE(d.Cin1 == 0 || op.x1, SDC_ENULL, "sdc_conv: Cin1 > 0 but x1 is null");
+    SDC_REQUIRE(d.kD > 0 && d.kH > 0 && d.kW > 0 && d.sD > 0 && d.sH > 0 && d.sW > 0, SDC_EINVAL,
+                "sdc_conv: bad kernel/stride");
+    SDC_REQUIRE(d.precision == 0 || (d.precision >= 2 && d.precision <= 7), SDC_EINVAL, "sdc_conv: precision must be 0 (fp32 MFMA, direct form), 2 (fp32 Winograd along W), 3 (fp32 Winograd over H and W), 4 (fp32 Winograd over D, H and W), 5 (as 4, F(4,3) for the 1-D convs), 6 (as 4, fp16 operands for the 3-tap convs where measured faster) or 7 (as 6 on every covered 3-tap conv)");
+    SDC_REQUIRE(!gn || d.precision >= 2, SDC_EINVAL, "sdc_conv_gn: fused GroupNorm statistics need precision 2, 3 or 4 (sdc_conv_gnparts returned 0)");
+    SDC_REQUIRE(ilog2_exact(d.uD) >= 0 && ilog2_exact(d.uH) >= 0 && ilog2_exact(d.uW) >= 0, SDC_EINVAL, "sdc_conv: upsample factors must be 1, 2 or 4");
+    // output size must agree with what the gather will produce
+    auto osz = [](int i, int u, int mode, int k, int s, int p) {
+        const int v = mode ? (i - 1) * u + 1 : i * u;
+        return (v + 2 * p - k) / s + 1;
+    };
+    // (up to k-1 extra positions per axis are allowed: they read the implicit zeros past the far edge -- one-sided padding,
+    // used by the sub-pixel form of the stride-2 transposed conv; a shorter axis computes a prefix)
+    auto fits = [&](int o, int i, int u, int k, int st, int p) { return o >= 1 && o <= osz(i, u, d.up_mode, k, st, p) + (k - 1); };
+    SDC_REQUIRE(fits(d.oD, d.iD, d.uD, d.kD, d.sD, d.pD) && fits(d.oH, d.iH, d.uH, d.kH, d.sH, d.pH) && fits(d.oW, d.iW, d.uW, d.kW, d.sW, d.pW),
+                SDC_EINVAL, "sdc_conv: output size (%d,%d,%d) inconsistent with input/kernel/stride/pad", d.oD, d.oH, d.oW);
+    SDC_REQUIRE((int64_t)d.B * d.oD * d.oH * d.oW < (1ll << 31), SDC_EINVAL, "sdc_conv: too many output positions");
+    return SDC_OK;
 }
 
 int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const float* wp, const float* bias,
@@ -1750,20 +1907,9 @@ extern "C" int sdc_conv_dgrad_f16(const SdcConvDesc* dp, const float* g, const f
 // 3x3 convs of the Burgers net on 64 workgroups: the input channels are split over up to 8 workgroups per output tile, the
 // partial outputs go to `work` and are summed in split order (deterministic).  Other shapes: exactly sdc_conv.
 extern "C" size_t sdc_conv_splitk_bytes(const SdcConvDesc* dp) {
-    if (!dp) return 0;                               // (every form below checks the precision it needs itself; the direct forms need none)
-    static const int no_rh = exp_env("SDC_NO_ROWHALO");
-    if (dp->precision == 6 || dp->precision == 7) { SdcConvDesc d4 = *dp; d4.precision = 4; return sdc_conv_splitk_bytes(&d4); }   // (precision 4's split kernels)
+    if (!dp) return 0;
     const SdcConvDesc& d = *dp;
-    if (wg3s_ok(d, conv_small(d), !no_rh) || wg3_ok(d, conv_small(d), !no_rh)) return 0;
-    int S;
-    if (wg2_ok(d, conv_small(d), !no_rh)) S = wg2_ksplit(d);
-    else {
-        const int64_t ntot = (int64_t)d.B * d.oD * d.oH * d.oW;
-        const WgPick wgp = wg_pick(d, ntot, conv_small(d), !no_rh);
-        if (wgp.pick) S = (d.oW % 4 == 0 && d.ys[4] == 1) ? wg1_ksplit(d, wgp, ntot) : 1;
-        else S = (d.oW % 4 == 0 && d.precision != 5)
-                     ? direct_ksplit(d, ntot, (d.Cin0 % 16 == 0) && (d.Cin1 % 16 == 0) && conv_small(d)) : 1;
-    }
+    const int S = route(d, CANONICAL, 0, true).ksplit;
     return S > 1 ? (size_t)S * d.B * d.Cout * d.oD * d.oH * d.oW * sizeof(float) : 0;
 }
 
@@ -1773,23 +1919,7 @@ extern "C" int sdc_conv_splitk(const SdcConvDesc* dp, const float* x0, const flo
 }
 
 extern "C" int sdc_conv_gnparts(const SdcConvDesc* dp, int G) {
-    if (!dp) return 0;
-    if (dp->precision == 6 || dp->precision == 7) {
-        if (f16_ok(*dp)) return f16_gnparts(*dp, G);
-        SdcConvDesc d4 = *dp; d4.precision = 4;
-        return sdc_conv_gnparts(&d4, G);
-    }
-    static const int no_rh = exp_env("SDC_NO_ROWHALO");
-    const int64_t ntot = (int64_t)dp->B * dp->oD * dp->oH * dp->oW;
-    static const int no_wg2 = exp_env("SDC_NO_WG2");
-    static const int no_wg3 = exp_env("SDC_NO_WG3");
-    static const int old_wg3 = exp_env("SDC_WG3_OLD");
-    if (!no_wg2 && !no_wg3 && !old_wg3 && wg3s_ok(*dp, conv_small(*dp), !no_rh)) return gn_parts_for(*dp, WgPick{22, W2_BM, W3S_TILES * 8, false}, G);
-    if (!no_wg2 && !no_wg3 && wg3_ok(*dp, conv_small(*dp), !no_rh)) return gn_parts_for(*dp, WgPick{21, W2_BM, W2_TILES * 8, false}, G);
-    static const int no_wg2s = exp_env("SDC_NO_WG2S");
-    if (!no_wg2 && !no_wg2s && wg2s_ok(*dp, conv_small(*dp), !no_rh)) return gn_parts_for(*dp, WgPick{23, W2_BM, W3S_TILES * 4, false}, G);
-    if (!no_wg2 && wg2_ok(*dp, conv_small(*dp), !no_rh)) return gn_parts_for(*dp, WgPick{20, W2_BM, W2_TILES * 4, false}, G);
-    return gn_parts_for(*dp, wg_pick(*dp, ntot, conv_small(*dp), !no_rh), G);
+    return dp ? route(*dp, CANONICAL, G, false).gn_parts : 0;
 }
 
 extern "C" int sdc_conv_gn(const SdcConvDesc* dp, const float* x0, const float* x1, const float* wp, const float* bias,
@@ -1800,15 +1930,10 @@ extern "C" int sdc_conv_gn(const SdcConvDesc* dp, const float* x0, const float* 
 
 extern "C" int sdc_conv_describe(const SdcConvDesc* dp, char* name, size_t cap, double* mfma_share) {
     SDC_REQUIRE(dp, SDC_ENULL, "sdc_conv_describe: null descriptor");
-    float* const dummy = reinterpret_cast<float*>(uintptr_t(256));   // aligned, never dereferenced: nothing is launched
-    tl_describe = true;
-    tl_pick = "";
-    tl_factor = 1.0;
-    const int rc = conv_impl(dp, dummy, dp->Cin1 > 0 ? dummy : nullptr, dummy, nullptr, nullptr, dummy, nullptr, 0, nullptr);
-    tl_describe = false;
-    if (rc != SDC_OK) return rc;
-    if (name && cap) { std::strncpy(name, tl_pick, cap - 1); name[cap - 1] = 0; }
-    if (mfma_share) *mfma_share = tl_factor;
+    { const int rc = check_conv(*dp, CANONICAL, false); if (rc != SDC_OK) return rc; }
+    const Route r = route(*dp, CANONICAL, 0, false);
+    if (name && cap) { std::strncpy(name, r.name, cap - 1); name[cap - 1] = 0; }
+    if (mfma_share) *mfma_share = r.share;
     return SDC_OK;
 }
 
@@ -1819,321 +1944,100 @@ int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const flo
               const int32_t* gexp) {
     SDC_REQUIRE(dp && x0 && wp && y, SDC_ENULL, "sdc_conv: null pointer");
     const SdcConvDesc& d = *dp;
-    SDC_REQUIRE(d.B > 0 && d.Cin0 > 0 && d.Cin1 >= 0 && d.Cout > 0, SDC_EINVAL, "sdc_conv: bad channel/batch counts");
-    SDC_REQUIRE(d.Cin1 == 0 || x1, SDC_ENULL, "sdc_conv: Cin1 > 0 but x1 is null");
-    SDC_REQUIRE(d.kD > 0 && d.kH > 0 && d.kW > 0 && d.sD > 0 && d.sH > 0 && d.sW > 0, SDC_EINVAL,
-                "sdc_conv: bad kernel/stride");
-    SDC_REQUIRE(d.precision == 0 || (d.precision >= 2 && d.precision <= 7), SDC_EINVAL, "sdc_conv: precision must be 0 (fp32 MFMA, direct form), 2 (fp32 Winograd along W), 3 (fp32 Winograd over H and W), 4 (fp32 Winograd over D, H and W), 5 (as 4, F(4,3) for the 1-D convs), 6 (as 4, fp16 operands for the 3-tap convs where measured faster) or 7 (as 6 on every covered 3-tap conv)");
-    SDC_REQUIRE(!gn_part || d.precision >= 2, SDC_EINVAL, "sdc_conv_gn: fused GroupNorm statistics need precision 2, 3 or 4 (sdc_conv_gnparts returned 0)");
-    // the caller sized `parts` with sdc_conv_gnparts(d, G), which sees the descriptor only: a kernel picked here on other
-    // grounds (pointer alignment, a residual) with a different part count would write a table the finalize pass misreads
-    const int gn_expect = gn_part ? sdc_conv_gnparts(dp, gn_G) : 0;
-#define SDC_GN_PARTS_AGREE(n) SDC_REQUIRE((n) == gn_expect, SDC_EINVAL, "sdc_conv_gn: this call runs a kernel with %d partial sums per group where sdc_conv_gnparts promised %d (misaligned pointers or a residual the descriptor does not show?)", (n), gn_expect)
+    const Operands op{x0, x1, wp, y, residual};
+    { const int rc = check_conv(d, op, gn_part != nullptr); if (rc != SDC_OK) return rc; }
+    const Route r = route(d, op, gn_part ? gn_G : 0, split_work != nullptr);
+    if (gn_part) {
+        SDC_REQUIRE(r.gn_parts > 0, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
+        // the caller sized `parts` with sdc_conv_gnparts(d, G), which sees the descriptor only: a kernel picked here on other
+        // grounds (pointer alignment, a residual) with a different part count would write a table the finalize pass misreads
+        const Route want = route(d, CANONICAL, gn_G, false);
+        SDC_REQUIRE(r.gn_parts == want.gn_parts, SDC_EINVAL, "sdc_conv_gn: %s, so this call runs %s with %d partial sums per group where sdc_conv_gnparts promised %d (%s)",
+                    wino_misfit(d, op).c_str(), r.name, r.gn_parts, want.gn_parts, want.name);
+    }
     ConvArgs a;
     a.d = d;
+    if (r.kern != Kern::F16 && d.precision >= 6) a.d.precision = 4;      // (precision 6 / 7 on precision 4's kernels)
     a.lgD = ilog2_exact(d.uD); a.lgH = ilog2_exact(d.uH); a.lgW = ilog2_exact(d.uW);
-    SDC_REQUIRE(a.lgD >= 0 && a.lgH >= 0 && a.lgW >= 0, SDC_EINVAL, "sdc_conv: upsample factors must be 1, 2 or 4");
-    // output size must agree with what the gather will produce
-    auto osz = [](int i, int u, int mode, int k, int s, int p) {
-        const int v = mode ? (i - 1) * u + 1 : i * u;
-        return (v + 2 * p - k) / s + 1;
-    };
-    // (up to k-1 extra positions per axis are allowed: they read the implicit zeros past the far edge -- one-sided padding,
-    // used by the sub-pixel form of the stride-2 transposed conv; a shorter axis computes a prefix)
-    auto fits = [&](int o, int i, int u, int k, int st, int p) { return o >= 1 && o <= osz(i, u, d.up_mode, k, st, p) + (k - 1); };
-    SDC_REQUIRE(fits(d.oD, d.iD, d.uD, d.kD, d.sD, d.pD) && fits(d.oH, d.iH, d.uH, d.kH, d.sH, d.pH) && fits(d.oW, d.iW, d.uW, d.kW, d.sW, d.pW),
-                SDC_EINVAL, "sdc_conv: output size (%d,%d,%d) inconsistent with input/kernel/stride/pad", d.oD, d.oH, d.oW);
-    const int64_t ntot = (int64_t)d.B * d.oD * d.oH * d.oW;
-    SDC_REQUIRE(ntot < (1ll << 31), SDC_EINVAL, "sdc_conv: too many output positions");
     a.x0 = x0; a.x1 = x1; a.wp = wp; a.bias = bias; a.res = residual; a.y = y;
-    a.Ntot = (int)ntot;
+    a.Ntot = d.B * d.oD * d.oH * d.oW;
     a.Cin = d.Cin0 + d.Cin1;
     a.Ktot = d.kD * d.kH * d.kW * a.Cin;
-    // FAST: whole K chunks share a tap, and every per-thread offset fits the 32-bit voffset of the saddr load form
-    const bool small = conv_small(d);
-    static const int no_rh = exp_env("SDC_NO_ROWHALO");
-    a.rowhalo = !no_rh;
-    a.vec2 = 0;
-    {
-        auto dense = [&](const int64_t* st) { return st[4] == 1 && st[3] == d.oW && st[2] == (int64_t)d.oH * d.oW; };
-        const int64_t S = (int64_t)d.oD * d.oH * d.oW;
-        a.ydense = dense(d.ys) && S >= 128 && S < (1 << 24) && span5(d.ys, d.B, d.Cout, d.oD, d.oH, d.oW) < (1ll << 30) &&
-                   (!residual || (dense(d.rs) && span5(d.rs, d.B, d.Cout, d.oD, d.oH, d.oW) < (1ll << 30)));
-        static const int no_dense = exp_env("SDC_NO_DENSE_EPI");
-        if (no_dense) a.ydense = 0;
-    }
+    // Winograd epilogues: rows of y (and of the residual) allow 8-byte accesses at even positions
+    auto even = [](const int64_t* st) { return st[4] == 1 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0 && st[3] % 2 == 0; };
+    a.vec2 = even(d.ys) && aligned(y, 8) && (!residual || (even(d.rs) && aligned(residual, 8)));
+    a.ydense = y_dense(d, residual != nullptr);
     a.wg2 = nullptr;
     a.gn_part = nullptr; a.gn_G = a.gn_cpg = a.gn_nparts = a.gn_S = 0;
+    if (gn_part) { a.gn_part = gn_part; a.gn_G = gn_G; a.gn_cpg = d.Cout / gn_G; a.gn_nparts = r.gn_parts; a.gn_S = d.oD * d.oH * d.oW; }
     a.ksplit = 1; a.ypart_elems = 0;
-    const bool fast = (d.Cin0 % BK == 0) && (d.Cin1 % BK == 0) && small && d.Cout < (1 << 30);
+    // sdc_conv_splitk: r.ksplit workgroups per output tile, each writing a dense partial copy of y into the caller's workspace;
+    // splitk_sum_kernel sums them in split order (deterministic) into y
+    const int64_t elems = (int64_t)d.B * d.Cout * d.oD * d.oH * d.oW;
+    if (r.ksplit > 1) {
+        SDC_REQUIRE(split_bytes >= (size_t)r.ksplit * elems * sizeof(float), SDC_EINVAL, "sdc_conv_splitk: workspace too small");
+        SDC_REQUIRE(aligned(split_work, 16), SDC_EINVAL, "sdc_conv_splitk: workspace must be 16-byte aligned");
+        SDC_REQUIRE(elems <= (1ll << 30), SDC_EINVAL, "sdc_conv_splitk: partial copy too large");
+        a.ksplit = r.ksplit; a.ypart_elems = elems; a.y = split_work;
+        a.d.ys[4] = 1; a.d.ys[3] = d.oW; a.d.ys[2] = (int64_t)d.oH * d.oW; a.d.ys[1] = a.d.ys[2] * d.oD; a.d.ys[0] = a.d.ys[1] * d.Cout;
+        a.vec2 = 1;
+        a.ydense = (int64_t)d.oD * d.oH * d.oW >= 128 && (int64_t)d.oD * d.oH * d.oW < (1 << 24);
+        if (r.sum_bias) a.bias = nullptr;
+    }
     hipStream_t s = sdc::as_stream(stream);
-    auto even = [](const int64_t* st) { return st[4] == 1 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0 && st[3] % 2 == 0; };
-    // precision 6 / 7: fp16 operands, fp32 accumulation (sdc_conv_f16.hip) for the covered 3-tap convs (6: those of the measured
-    // dispatch table); the other convs, and sdc_conv_splitk, run precision 4's kernels on the buffer's precision-4 prefix
-    if (d.precision == 6 || d.precision == 7) {
-        if (!split_work && f16_ok(d)) {
-            if (gn_part) {
-                a.gn_nparts = f16_gnparts(d, gn_G);
-                SDC_REQUIRE(a.gn_nparts > 0, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
-                SDC_GN_PARTS_AGREE(a.gn_nparts);
-                a.gn_part = gn_part; a.gn_G = gn_G; a.gn_cpg = d.Cout / gn_G; a.gn_S = d.oD * d.oH * d.oW;
-            }
-            SDC_PICK(f16_name(d), 1.0);
+    const float* const taps2 = wp + (int64_t)a.Ktot * d.Cout + (int64_t)(a.Ktot / 3 * 4) * d.Cout;     // F(2x2,3x3) taps (precision 3)
+    int rc = SDC_OK;
+    switch (r.kern) {
+        case Kern::F16: {
             const size_t off = (sdc_pack_conv_weight_floats(d.Cout, a.Cin, d.kD, d.kH, d.kW, 4) + 3) & ~(size_t)3;   // 16-byte aligned tail
             return launch_f16(a, reinterpret_cast<const _Float16*>(wp + off), s, gexp);
         }
-        SdcConvDesc d4 = d;
-        d4.precision = 4;
-        return conv_impl(&d4, x0, x1, wp, bias, residual, y, gn_part, gn_G, stream, split_work, split_bytes);
-    }
-    static const int no_wg2 = exp_env("SDC_NO_WG2");
-    static const int no_wg3 = exp_env("SDC_NO_WG3");
-    // fp32 Winograd F(2x2x2,3x3x3), two workgroups per CU (round 5): 3x3x3 stride-1 convs over whole rows, plane pairs
-    static const int old_wg3 = exp_env("SDC_WG3_OLD");
-    if (!no_wg2 && !no_wg3 && !old_wg3 && wg3s_ok(d, small, a.rowhalo != 0) && reinterpret_cast<uintptr_t>(wp) % 16 == 0 &&
-        reinterpret_cast<uintptr_t>(x0) % 16 == 0 && (d.Cin1 == 0 || reinterpret_cast<uintptr_t>(x1) % 16 == 0) &&
-        reinterpret_cast<uintptr_t>(y) % 8 == 0 && !residual) {
-        a.vec2 = 1;
-        a.wg2 = wp + (int64_t)a.Ktot * d.Cout + (int64_t)(a.Ktot / 3 * 4) * d.Cout + (int64_t)(a.Ktot / 9 * 16) * d.Cout;
-        if (gn_part) {
-            a.gn_nparts = gn_parts_for(d, WgPick{22, W2_BM, W3S_TILES * 8, false}, gn_G);
-            SDC_REQUIRE(a.gn_nparts > 0, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
-            SDC_GN_PARTS_AGREE(a.gn_nparts);
-            a.gn_part = gn_part; a.gn_G = gn_G; a.gn_cpg = d.Cout / gn_G; a.gn_S = d.oD * d.oH * d.oW;
-        }
-        SDC_PICK(d.oW == 16 ? "conv_wg3s_kernel<16>" : (d.oW == 32 ? "conv_wg3s_kernel<32>" : "conv_wg3s_kernel<64>"), 8.0 / 27.0);
-        { const int rc_ = launch_wg3s(a, s); if (rc_) return rc_; }
-        return sdc::check_launch("sdc_conv[winograd 2x2x2, two workgroups per CU]");
-    }
-    // fp32 Winograd F(2x2x2,3x3x3), one workgroup per CU: the shapes the form above does not take
-    if (!no_wg2 && !no_wg3 && wg3_ok(d, small, a.rowhalo != 0) && reinterpret_cast<uintptr_t>(wp) % 16 == 0 &&
-        reinterpret_cast<uintptr_t>(x0) % 16 == 0 && (d.Cin1 == 0 || reinterpret_cast<uintptr_t>(x1) % 16 == 0) &&
-        reinterpret_cast<uintptr_t>(y) % 8 == 0 && !residual) {
-        a.vec2 = 1;
-        a.wg2 = wp + (int64_t)a.Ktot * d.Cout + (int64_t)(a.Ktot / 3 * 4) * d.Cout + (int64_t)(a.Ktot / 9 * 16) * d.Cout;
-        if (gn_part) {
-            a.gn_nparts = gn_parts_for(d, WgPick{21, W2_BM, W2_TILES * 8, false}, gn_G);
-            SDC_REQUIRE(a.gn_nparts > 0, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
-            SDC_GN_PARTS_AGREE(a.gn_nparts);
-            a.gn_part = gn_part; a.gn_G = gn_G; a.gn_cpg = d.Cout / gn_G; a.gn_S = d.oD * d.oH * d.oW;
-        }
-        SDC_PICK(d.oW == 16 ? "conv_wg3_kernel<16>" : (d.oW == 32 ? "conv_wg3_kernel<32>" : "conv_wg3_kernel<64>"), 8.0 / 27.0);
-        { const int rc_ = launch_wg3(a, s); if (rc_) return rc_; }
-        return sdc::check_launch("sdc_conv[winograd 2x2x2]");
-    }
-    // fp32 Winograd F(2x2,3x3), two workgroups per CU (round 6): 3x3 convs (kD = 1) over whole rows of 128 / 64 / 32 -- unless
-    // sdc_conv_splitk wants to split this conv (small grids keep the one-workgroup form and its Cin split)
-    static const int no_wg2s = exp_env("SDC_NO_WG2S");
-    if (!no_wg2 && !no_wg2s && wg2s_ok(d, small, a.rowhalo != 0) && reinterpret_cast<uintptr_t>(wp) % 16 == 0 &&
-        reinterpret_cast<uintptr_t>(x0) % 16 == 0 && (d.Cin1 == 0 || reinterpret_cast<uintptr_t>(x1) % 16 == 0) &&
-        reinterpret_cast<uintptr_t>(y) % 8 == 0 && !residual && !(split_work && wg2_ksplit(d) > 1)) {
-        a.vec2 = 1;
-        a.wg2 = wp + (int64_t)a.Ktot * d.Cout + (int64_t)(a.Ktot / 3 * 4) * d.Cout;
-        if (gn_part) {
-            a.gn_nparts = gn_parts_for(d, WgPick{23, W2_BM, W3S_TILES * 4, false}, gn_G);
-            SDC_REQUIRE(a.gn_nparts > 0, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
-            SDC_GN_PARTS_AGREE(a.gn_nparts);
-            a.gn_part = gn_part; a.gn_G = gn_G; a.gn_cpg = d.Cout / gn_G; a.gn_S = d.oD * d.oH * d.oW;
-        }
-        SDC_PICK(d.oW == 128 ? "conv_wg2s_kernel<128>" : (d.oW == 64 ? "conv_wg2s_kernel<64>" : "conv_wg2s_kernel<32>"), 4.0 / 9.0);
-        { const int rc_ = launch_wg2s(a, s); if (rc_) return rc_; }
-        return sdc::check_launch("sdc_conv[winograd 2x2, two workgroups per CU]");
-    }
-    // fp32 Winograd F(2x2,3x3) over (H, W): 3x3 / 3x3x3 stride-1 convs over whole rows
-    if (!no_wg2 && wg2_ok(d, small, a.rowhalo != 0) && reinterpret_cast<uintptr_t>(wp) % 16 == 0 &&
-        reinterpret_cast<uintptr_t>(x0) % 16 == 0 && (d.Cin1 == 0 || reinterpret_cast<uintptr_t>(x1) % 16 == 0)) {
-        a.vec2 = even(d.ys) && reinterpret_cast<uintptr_t>(y) % 8 == 0 &&
-                 (!residual || (even(d.rs) && reinterpret_cast<uintptr_t>(residual) % 8 == 0));
-        a.wg2 = wp + (int64_t)a.Ktot * d.Cout + (int64_t)(a.Ktot / 3 * 4) * d.Cout;
-        a.lgW = ilog2_pow2(d.oW);
-        if (gn_part) {
-            a.gn_nparts = gn_parts_for(d, WgPick{20, W2_BM, W2_TILES * 4, false}, gn_G);
-            SDC_REQUIRE(a.gn_nparts > 0, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
-            SDC_GN_PARTS_AGREE(a.gn_nparts);
-            a.gn_part = gn_part; a.gn_G = gn_G; a.gn_cpg = d.Cout / gn_G; a.gn_S = d.oD * d.oH * d.oW;
-        }
-        SDC_PICK(d.oW == 16 ? "conv_wg2_kernel<16>" : (d.oW == 32 ? "conv_wg2_kernel<32>" : (d.oW == 64 ? "conv_wg2_kernel<64>" : "conv_wg2_kernel<128>")),
-                 4.0 / 9.0);
-        // sdc_conv_splitk: Cin split over ksplit workgroups per tile into the caller's partial buffer, summed in split order
-        const int S = (split_work && !gn_part && !residual && !tl_describe) ? wg2_ksplit(d) : 1;
-        if (S > 1) {
-            const int64_t elems = (int64_t)d.B * d.Cout * d.oD * d.oH * d.oW;
-            SDC_REQUIRE(split_bytes >= (size_t)S * elems * sizeof(float), SDC_EINVAL, "sdc_conv_splitk: workspace too small");
-            SDC_REQUIRE(reinterpret_cast<uintptr_t>(split_work) % 16 == 0, SDC_EINVAL, "sdc_conv_splitk: workspace must be 16-byte aligned");
-            ConvArgs p = a;
-            p.ksplit = S; p.ypart_elems = elems; p.y = split_work; p.vec2 = 1;
-            p.d.ys[4] = 1; p.d.ys[3] = d.oW; p.d.ys[2] = (int64_t)d.oH * d.oW; p.d.ys[1] = p.d.ys[2] * d.oD; p.d.ys[0] = p.d.ys[1] * d.Cout;
-            SDC_REQUIRE(span5(p.d.ys, d.B, 8, d.oD, d.oH, d.oW) < (1ll << 30), SDC_EINVAL, "sdc_conv_splitk: partial copy too large");
-            { const int rc_ = launch_wg2(p, s); if (rc_) return rc_; }
-            const int64_t nq = elems / 4;                     // oW is a multiple of 16 here
-            hipLaunchKernelGGL(splitk_sum_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (const float*)split_work, y, S, elems,
-                               d.Cout, d.oD, d.oH, d.oW, d.ys[0], d.ys[1], d.ys[2], d.ys[3], d.ys[4]);
-            return sdc::check_launch("sdc_conv_splitk[winograd 2x2]");
-        }
-        { const int rc_ = launch_wg2(a, s); if (rc_) return rc_; }
-        return sdc::check_launch("sdc_conv[winograd 2x2]");
-    }
-    // fp32 Winograd F(2,3) along W: 3-wide stride-1 taps, whole 16-channel chunks, even rows
-    const WgPick wgp = wg_pick(d, ntot, small, a.rowhalo != 0);
-    if (wgp.pick && reinterpret_cast<uintptr_t>(wp) % 16 == 0) {
-        a.vec2 = even(d.ys) && reinterpret_cast<uintptr_t>(y) % 8 == 0 &&
-                 (!residual || (even(d.rs) && reinterpret_cast<uintptr_t>(residual) % 8 == 0));
-        if (gn_part) {
-            a.gn_nparts = gn_parts_for(d, wgp, gn_G);
-            SDC_REQUIRE(a.gn_nparts > 0, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
-            SDC_GN_PARTS_AGREE(a.gn_nparts);
-            a.gn_part = gn_part; a.gn_G = gn_G; a.gn_cpg = d.Cout / gn_G; a.gn_S = d.oD * d.oH * d.oW;
-        }
-        // sdc_conv_splitk on the 1-D form: Cin split over S workgroups per tile into the caller's partial buffer, summed in split
-        // order (+ bias) by splitk_sum_kernel
-        const int S1d = (split_work && !gn_part && !residual && !tl_describe && d.oW % 4 == 0 && d.ys[4] == 1) ? wg1_ksplit(d, wgp, ntot) : 1;
-        if (S1d > 1) {
-            const int64_t elems = (int64_t)d.B * d.Cout * d.oD * d.oH * d.oW;
-            SDC_REQUIRE(split_bytes >= (size_t)S1d * elems * sizeof(float), SDC_EINVAL, "sdc_conv_splitk: workspace too small");
-            SDC_REQUIRE(reinterpret_cast<uintptr_t>(split_work) % 16 == 0, SDC_EINVAL, "sdc_conv_splitk: workspace must be 16-byte aligned");
-            ConvArgs p = a;
-            p.ksplit = S1d; p.ypart_elems = elems; p.y = split_work; p.vec2 = 1; p.bias = nullptr;
-            p.d.ys[4] = 1; p.d.ys[3] = d.oW; p.d.ys[2] = (int64_t)d.oH * d.oW; p.d.ys[1] = p.d.ys[2] * d.oD; p.d.ys[0] = p.d.ys[1] * d.Cout;
-            if (wgp.ups) {
-                SDC_PICK("conv_wg_kernel<64,128,2,2,16,256,ups>", 2.0 / 3.0);
-                { const int rc_ = launch_wg<64, 128, 2, 2, 16, 256, true>(p, s); if (rc_) return rc_; }
-            } else {
-                SDC_PICK("conv_wg_kernel<64,128,2,2,16,512,ks2>", 2.0 / 3.0);
-                { const int rc_ = launch_wg<64, 128, 2, 2, 16, 512, false, 4, 2>(p, s); if (rc_) return rc_; }
+        case Kern::WG3S: a.wg2 = taps2 + (int64_t)(a.Ktot / 9 * 16) * d.Cout; rc = launch_wg3s(a, s); break;
+        case Kern::WG3: a.wg2 = taps2 + (int64_t)(a.Ktot / 9 * 16) * d.Cout; rc = launch_wg3(a, s); break;
+        case Kern::WG2S: a.wg2 = taps2; rc = launch_wg2s(a, s); break;
+        case Kern::WG2: a.wg2 = taps2; a.lgW = ilog2_pow2(d.oW); rc = launch_wg2(a, s); break;
+        case Kern::WG1:
+            switch (r.tile) {
+                case 13: rc = launch_f43<128, 128, 4, 16>(a, s); break;
+                case 6: rc = r.ups ? launch_wg<128, 128, 4, 2, 16, 512, true>(a, s) : launch_wg<128, 128, 4, 2, 16, 512>(a, s); break;
+                case 7: rc = r.ups ? launch_wg<64, 256, 2, 4, 16, 512, true>(a, s) : launch_wg<64, 256, 2, 4, 16, 512>(a, s); break;
+                case 9: rc = launch_wg<128, 256, 4, 2, 16, 512>(a, s); break;     // (2 x 4 waves measured the same)
+                case 10: rc = launch_wg<64, 512, 1, 8, 16, 512>(a, s); break;     // (each wave: both 32-row tiles x 32 pairs; measured 3 % ahead of 1 x 2)
+                default:
+                    // small grids (fewer than 256 of the 128 x 128 tiles): 64 x 128 tiles, each stage's k-steps split over two waves per SIMD
+                    // (a lone wave per SIMD left the transform / staging VALU exposed: 68 TFLOP/s issued)
+                    rc = r.ups ? launch_wg<64, 128, 2, 2, 16, 256, true>(a, s) : launch_wg<64, 128, 2, 2, 16, 512, false, 4, 2>(a, s);
             }
-            const int64_t nq = elems / 4;
-            hipLaunchKernelGGL(splitk_sum_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (const float*)split_work, y, S1d, elems,
-                               d.Cout, d.oD, d.oH, d.oW, d.ys[0], d.ys[1], d.ys[2], d.ys[3], d.ys[4], bias);
-            return sdc::check_launch("sdc_conv_splitk[winograd 1-D]");
-        }
-        if (wgp.ups) {
-            if (wgp.pick == 6) { SDC_PICK("conv_wg_kernel<128,128,4,2,16,512,ups>", 2.0 / 3.0); { const int rc_ = launch_wg<128, 128, 4, 2, 16, 512, true>(a, s); if (rc_) return rc_; } }
-            else if (wgp.pick == 7) { SDC_PICK("conv_wg_kernel<64,256,2,4,16,512,ups>", 2.0 / 3.0); { const int rc_ = launch_wg<64, 256, 2, 4, 16, 512, true>(a, s); if (rc_) return rc_; } }
-            else { SDC_PICK("conv_wg_kernel<64,128,2,2,16,256,ups>", 2.0 / 3.0); { const int rc_ = launch_wg<64, 128, 2, 2, 16, 256, true>(a, s); if (rc_) return rc_; } }
-            return sdc::check_launch("sdc_conv[winograd,upsample]");
-        }
-        if (wgp.pick == 13) { SDC_PICK("conv_f43_kernel<128,128,4,16,F43>", 0.5); { const int rc_ = launch_f43<128, 128, 4, 16>(a, s); if (rc_) return rc_; } }
-        else if (wgp.pick == 6) { SDC_PICK("conv_wg_kernel<128,128,4,2,16,512>", 2.0 / 3.0); { const int rc_ = launch_wg<128, 128, 4, 2, 16, 512>(a, s); if (rc_) return rc_; } }
-        else if (wgp.pick == 7) { SDC_PICK("conv_wg_kernel<64,256,2,4,16,512>", 2.0 / 3.0); { const int rc_ = launch_wg<64, 256, 2, 4, 16, 512>(a, s); if (rc_) return rc_; } }
-        else if (wgp.pick == 9) { SDC_PICK("conv_wg_kernel<128,256,4,2,16,512>", 2.0 / 3.0); { const int rc_ = launch_wg<128, 256, 4, 2, 16, 512>(a, s); if (rc_) return rc_; } }       // (2 x 4 waves measured the same)
-        else if (wgp.pick == 10) { SDC_PICK("conv_wg_kernel<64,512,1,8,16,512>", 2.0 / 3.0); { const int rc_ = launch_wg<64, 512, 1, 8, 16, 512>(a, s); if (rc_) return rc_; } }     // (each wave: both 32-row tiles x 32 pairs; measured 3 % ahead of 1 x 2)
-        else {
-            // small grids (fewer than 256 of the 128 x 128 tiles): 64 x 128 tiles, each stage's k-steps split over two waves per SIMD
-            // (a lone wave per SIMD left the transform / staging VALU exposed: 68 TFLOP/s issued)
-            SDC_PICK("conv_wg_kernel<64,128,2,2,16,512,ks2>", 2.0 / 3.0);
-            { const int rc_ = launch_wg<64, 128, 2, 2, 16, 512, false, 4, 2>(a, s); if (rc_) return rc_; }
-        }
-        return sdc::check_launch("sdc_conv[winograd]");
-    }
-    SDC_REQUIRE(!gn_part, SDC_EINVAL, "sdc_conv_gn: shape not covered by the fused statistics (sdc_conv_gnparts returned 0)");
-    // pointwise convs over a dense layout: 16-byte loads of weights and activations
-    static const int no_pw = exp_env("SDC_NO_PW");
-    {
-        const int64_t S = (int64_t)d.oD * d.oH * d.oW;
-        auto dense = [&](const int64_t* st) { return st[4] == 1 && st[3] == d.iW && st[2] == (int64_t)d.iH * d.iW && st[0] % 4 == 0 && st[1] % 4 == 0; };
-        const bool pw_shape = !no_pw && fast && d.kD * d.kH * d.kW == 1 && d.sD == 1 && d.sH == 1 && d.sW == 1 && d.uD == 1 && d.uH == 1 &&
-            d.uW == 1 && d.up_mode == 0 && d.pD == 0 && d.pH == 0 && d.pW == 0 && d.oD == d.iD && d.oH == d.iH && d.oW == d.iW &&
-            S % 4 == 0 && d.Cout % 4 == 0 && d.Cout > 32 && dense(d.x0s) && (d.Cin1 == 0 || dense(d.x1s)) &&
-            reinterpret_cast<uintptr_t>(x0) % 16 == 0 && (d.Cin1 == 0 || reinterpret_cast<uintptr_t>(x1) % 16 == 0) &&
-            reinterpret_cast<uintptr_t>(wp) % 16 == 0;
-        // sdc_conv_splitk on the direct-form kernels' smallest tile: K split over Sd workgroups per tile into the caller's partial
-        // buffer, summed in split order (+ bias) by splitk_sum_kernel
-        const int Sd = (split_work && !residual && !tl_describe && d.oW % 4 == 0 && d.precision != 5) ? direct_ksplit(d, ntot, fast) : 1;
-        if (Sd > 1) {
-            const int64_t elems = (int64_t)d.B * d.Cout * d.oD * d.oH * d.oW;
-            SDC_REQUIRE(split_bytes >= (size_t)Sd * elems * sizeof(float), SDC_EINVAL, "sdc_conv_splitk: workspace too small");
-            SDC_REQUIRE(reinterpret_cast<uintptr_t>(split_work) % 16 == 0, SDC_EINVAL, "sdc_conv_splitk: workspace must be 16-byte aligned");
-            ConvArgs p = a;
-            p.ksplit = Sd; p.ypart_elems = elems; p.y = split_work; p.bias = nullptr; p.res = nullptr;
-            p.d.ys[4] = 1; p.d.ys[3] = d.oW; p.d.ys[2] = (int64_t)d.oH * d.oW; p.d.ys[1] = p.d.ys[2] * d.oD; p.d.ys[0] = p.d.ys[1] * d.Cout;
-            SDC_REQUIRE(span5(p.d.ys, d.B, d.Cout, d.oD, d.oH, d.oW) < (1ll << 30), SDC_EINVAL, "sdc_conv_splitk: partial copy too large");
-            p.ydense = S >= 128 && S < (1 << 24);
-            if (pw_shape) {
-                SDC_PICK("conv_pw_kernel<64,64,2,2>", 1.0);
-                dim3 grid((unsigned)(((a.Ntot + 63) / 64) * ((d.Cout + 63) / 64)), (unsigned)Sd);
-                hipLaunchKernelGGL((conv_pw_kernel<64, 64, 2, 2>), grid, dim3(NT), 0, s, p);
-            } else {
-                SDC_PICK("conv_kernel<64,64,2,2,true>", 1.0);
-                dim3 grid((unsigned)((a.Ntot + 63) / 64), (unsigned)((d.Cout + 63) / 64), (unsigned)Sd);
-                hipLaunchKernelGGL((conv_kernel<64, 64, 2, 2, true>), grid, dim3(NT), 0, s, p);
+            break;
+        case Kern::PW2: rc = r.tile == 0 ? launch_pw2<2, 2>(a, s) : launch_pw2<1, 4>(a, s); break;
+        case Kern::PW:
+            switch (r.tile) {
+                case 0: launch_pw<128, 128, 2, 2>(a, s); break;
+                case 1: launch_pw<64, 256, 1, 4>(a, s); break;
+                case 2: launch_pw<64, 128, 2, 2>(a, s); break;
+                default: launch_pw<64, 64, 2, 2>(a, s);
             }
-            const int64_t nq = elems / 4;
-            hipLaunchKernelGGL(splitk_sum_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (const float*)split_work, y, Sd, elems,
-                               d.Cout, d.oD, d.oH, d.oW, d.ys[0], d.ys[1], d.ys[2], d.ys[3], d.ys[4], bias);
-            return sdc::check_launch("sdc_conv_splitk[direct]");
-        }
-        if (pw_shape) {
-            const int64_t b64x128 = (int64_t)((a.Ntot + 127) / 128) * ((d.Cout + 63) / 64);
-            // two-workgroups-per-CU form with interleaved tiles (round 5): whole 128-channel blocks, 16-byte aligned dense rows of y
-            // (and of the residual), enough 128 x 256 tiles for two rounds of the chip
-            static const int no_pw2 = exp_env("SDC_NO_PW2");
-            const bool al16 = reinterpret_cast<uintptr_t>(y) % 16 == 0 && d.ys[0] % 4 == 0 && d.ys[1] % 4 == 0 &&
-                              (!residual || (reinterpret_cast<uintptr_t>(residual) % 16 == 0 && d.rs[0] % 4 == 0 && d.rs[1] % 4 == 0));
-            if (!no_pw2 && d.Cout % 128 == 0 && a.ydense && al16 && (int64_t)((a.Ntot + 255) / 256) * (d.Cout / 128) >= 1024) {
-                SDC_PICK("conv_pw2_kernel<2,2>", 1.0);
-                { const int rc_ = launch_pw2<2, 2>(a, s); if (rc_) return rc_; }
-                return sdc::check_launch("sdc_conv[pointwise, two workgroups per CU]");
+            break;
+        case Kern::STEM:
+            hipLaunchKernelGGL((conv_rh_kernel<64, 128, 2, 2, 7, true, 8>), dim3((a.Ntot + 127) / 128, (d.Cout + 63) / 64), dim3(NT), 0, s, a);
+            break;
+        case Kern::DIRECT:
+            switch (r.tile) {
+                case 0: launch_direct<128, 128, 2, 2>(a, r.form, s); break;
+                case 1: launch_direct<64, 256, 1, 4>(a, r.form, s); break;
+                case 2: launch_direct<64, 128, 2, 2>(a, r.form, s); break;
+                case 3: launch_direct<64, 64, 2, 2>(a, r.form, s); break;
+                default: launch_direct<32, 128, 1, 4>(a, r.form, s);
             }
-            if (!no_pw2 && d.Cout == 64 && a.ydense && al16 && (a.Ntot + 511) / 512 >= 1024) {
-                SDC_PICK("conv_pw2_kernel<1,4>", 1.0);
-                { const int rc_ = launch_pw2<1, 4>(a, s); if (rc_) return rc_; }
-                return sdc::check_launch("sdc_conv[pointwise, two workgroups per CU]");
-            }
-            if (d.Cout > 64 && a.Ntot >= 128 * 256) { SDC_PICK("conv_pw_kernel<128,128,2,2>", 1.0); launch_pw<128, 128, 2, 2>(a, s); }
-            else if (d.Cout <= 64 && a.Ntot >= 256 * 1024) { SDC_PICK("conv_pw_kernel<64,256,1,4>", 1.0); launch_pw<64, 256, 1, 4>(a, s); }
-            else if (b64x128 >= 1024) { SDC_PICK("conv_pw_kernel<64,128,2,2>", 1.0); launch_pw<64, 128, 2, 2>(a, s); }
-            else { SDC_PICK("conv_pw_kernel<64,64,2,2>", 1.0); launch_pw<64, 64, 2, 2>(a, s); }
-            return sdc::check_launch("sdc_conv[pointwise]");
-        }
+            break;
     }
-    // stem convs (kW = 7, tiny Cin): row-halo kernel with generalized k rows
-    if (a.rowhalo && d.kW == 7 && d.sW == 1 && d.uD == 1 && d.uH == 1 && d.uW == 1 && d.up_mode == 0 && d.kD * d.kH <= 64 &&
-        d.Cout % 4 == 0 && d.Cout > 32 && small && ((d.oW % 128 == 0) || (128 % d.oW == 0 && d.oW >= 16)) &&
-        reinterpret_cast<uintptr_t>(wp) % 16 == 0) {
-        static const int stem_tile = exp_env("SDC_STEM_TILE");
-        if (stem_tile == 256 && (d.oW % 256 == 0 || 256 % d.oW == 0)) {
-            dim3 grid((a.Ntot + 255) / 256, (d.Cout + 63) / 64);
-            SDC_PICK("conv_rh_kernel<64,256,1,4,7,true>", 1.0);
-            hipLaunchKernelGGL((conv_rh_kernel<64, 256, 1, 4, 7, true>), grid, dim3(NT), 0, s, a);
-            return sdc::check_launch("sdc_conv[stem]");
-        }
-        if (stem_tile == 512 && (d.oW % 512 == 0 || 512 % d.oW == 0)) {
-            dim3 grid((a.Ntot + 511) / 512, (d.Cout + 63) / 64);
-            SDC_PICK("conv_rh_kernel<64,512,1,4,7,true>", 1.0);
-            hipLaunchKernelGGL((conv_rh_kernel<64, 512, 1, 4, 7, true>), grid, dim3(NT), 0, s, a);
-            return sdc::check_launch("sdc_conv[stem]");
-        }
-        dim3 grid((a.Ntot + 127) / 128, (d.Cout + 63) / 64);
-        SDC_PICK("conv_rh_kernel<64,128,2,2,7,true>", 1.0);
-        if (stem_tile == 16) hipLaunchKernelGGL((conv_rh_kernel<64, 128, 2, 2, 7, true, 16>), grid, dim3(NT), 0, s, a);
-        else hipLaunchKernelGGL((conv_rh_kernel<64, 128, 2, 2, 7, true, 8>), grid, dim3(NT), 0, s, a);
-        return sdc::check_launch("sdc_conv[stem]");
-    }
-    const int64_t blocks64x128 = (int64_t)((a.Ntot + 127) / 128) * ((d.Cout + 63) / 64);
-    static const int force_tile = exp_env("SDC_TILE");   // tuning knob: 1..5 picks a tile
-    if (force_tile && d.Cout > 32) {
-        switch (force_tile) {
-            case 1: SDC_LAUNCH(128, 128, 2, 2); break;
-            case 2: SDC_LAUNCH(64, 256, 1, 4); break;
-            case 3: SDC_LAUNCH(64, 128, 2, 2); break;
-            case 4: SDC_LAUNCH(64, 64, 2, 2); break;
-            default: SDC_LAUNCH(32, 128, 1, 4); break;
-        }
-        if (tl_describe) return SDC_OK;
-        return sdc::check_launch("sdc_conv");
-    }
-    if (d.Cout > 64 && a.Ntot >= 128 * 256)
-        SDC_LAUNCH(128, 128, 2, 2);
-    else if (d.Cout > 32 && d.Cout <= 64 && a.Ntot >= 256 * 1024)
-        SDC_LAUNCH(64, 256, 1, 4);     // wide tile: each wave owns 64x64 (2x2 MFMA tiles) like the 128x128 case
-    else if (d.Cout > 32 && blocks64x128 >= 1024)
-        SDC_LAUNCH(64, 128, 2, 2);
-    else if (d.Cout > 32)
-        SDC_LAUNCH(64, 64, 2, 2);      // small-N layers: twice the workgroups, >= 2 per CU
-    else
-        SDC_LAUNCH(32, 128, 1, 4);
-    if (tl_describe) return SDC_OK;
-    return sdc::check_launch("sdc_conv");
+    if (rc != SDC_OK) return rc;
+    if (r.ksplit > 1)
+        hipLaunchKernelGGL(splitk_sum_kernel, dim3((unsigned)((elems / 4 + 255) / 256)), dim3(256), 0, s, (const float*)split_work, y, r.ksplit,
+                           elems, d.Cout, d.oD, d.oH, d.oW, d.ys[0], d.ys[1], d.ys[2], d.ys[3], d.ys[4], r.sum_bias ? bias : nullptr);
+    const hipError_t e = hipGetLastError();
+    SDC_REQUIRE(e == hipSuccess, SDC_EHIP, "%s[%s]: %s", r.ksplit > 1 ? "sdc_conv_splitk" : "sdc_conv", r.name, hipGetErrorString(e));
+    return SDC_OK;
 }
 
 }  // namespace

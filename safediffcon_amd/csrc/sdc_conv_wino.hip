@@ -570,9 +570,9 @@ __global__ __launch_bounds__(256) void conv_wg2_kernel(const ConvArgs a) {
 }  // namespace
 
 // coverage of the F(2x2,3x3) kernel (precision 3)
-bool wg2_ok(const SdcConvDesc& d, bool small, bool rowhalo) {
+bool wg2_ok(const SdcConvDesc& d, bool small) {
     const int64_t rptot = (int64_t)d.B * d.oD * (d.oH / 2);
-    return d.precision >= 3 && rowhalo && small && d.kH == 3 && d.kW == 3 && (d.kD == 1 || d.kD == 3) &&
+    return d.precision >= 3 && small && d.kH == 3 && d.kW == 3 && (d.kD == 1 || d.kD == 3) &&
            d.sD == 1 && d.sH == 1 && d.sW == 1 && d.uD == 1 && d.uH == 1 && d.uW == 1 && d.up_mode == 0 &&
            d.pH == 1 && d.pW == 1 && d.pD == d.kD / 2 && d.oH == d.iH && d.oW == d.iW && d.oD == d.iD &&
            (d.oW == 16 || d.oW == 32 || d.oW == 64 || d.oW == 128) && d.oH % 2 == 0 &&
@@ -1097,12 +1097,12 @@ __global__ __launch_bounds__(256) void conv_wg3_kernel(const ConvArgs a) {
 
 // coverage of the F(2x2x2,3x3x3) kernel (precision 4): the F(2x2,3x3) shapes with kD = 3, an even depth, whole 64-channel
 // blocks, the row pairs of a workgroup inside one plane, 8-byte aligned rows of y (and of the residual)
-bool wg3_ok(const SdcConvDesc& d, bool small, bool rowhalo) {
+bool wg3_ok(const SdcConvDesc& d, bool small) {
     auto even = [](const int64_t* st) { return st[4] == 1 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0 && st[3] % 2 == 0; };
     if (!(d.precision >= 4 && d.kD == 3 && d.oD % 2 == 0 && (d.oW == 16 || d.oW == 32 || d.oW == 64) && d.Cout % W2_BM == 0)) return false;
     SdcConvDesc e = d;
     e.precision = 3;
-    if (!wg2_ok(e, small, rowhalo)) return false;
+    if (!wg2_ok(e, small)) return false;
     const int rp = W2_TILES / (d.oW / 2);
     const bool nores = d.rs[0] == 0 && d.rs[1] == 0 && d.rs[2] == 0 && d.rs[3] == 0 && d.rs[4] == 0;     // (a fused residual: the F(2x2,3x3) kernel)
     return (d.oH / 2) % rp == 0 && even(d.ys) && nores;
@@ -1145,7 +1145,7 @@ int launch_wg3(const ConvArgs& a, hipStream_t s) {
 
 // coverage of conv_wg3s_kernel (the two-workgroups-per-CU form of the F(2x2x2,3x3x3) kernel): what conv_wg3_kernel takes with 32
 // instead of 64 tiles per workgroup, and one channel stride for both inputs (the lane offsets of the gather are stage-invariant)
-bool wg3s_ok(const SdcConvDesc& d, bool small, bool rowhalo) {
+bool wg3s_ok(const SdcConvDesc& d, bool small) {
     auto even = [](const int64_t* st) { return st[4] == 1 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0 && st[3] % 2 == 0; };
     // Rows of 64 and of 32.  Same-box A/B at C4, B = 64 (profiles/r5_ab_wg3s.log): they win in isolation on every box (64 -> 64:
     // 5.74 -> 5.33 ms, 64 -> 128 @ 32: 2.72 -> 2.55, 128 -> 128 @ 32: 4.91 -> 4.79) and move fewer bytes through the fabric (PMC:
@@ -1154,11 +1154,9 @@ bool wg3s_ok(const SdcConvDesc& d, bool small, bool rowhalo) {
     // and 4.78 / 4.93, 256 + 256 -> 128: 4.59 / 4.69), the whole step is the same to 0.15 % (238.1 / 237.7 ms), and with four
     // channel tiles per position tile and half the positions per workgroup this form fetches more (6.5 x against 5.6 x).
     if (!(d.precision >= 4 && d.kD == 3 && d.oD % 2 == 0 && d.Cout % W2_BM == 0 && (d.oW == 64 || d.oW == 32))) return false;
-    static const int no32w = exp_env("SDC_WG3S_NO32WIDE");     // (experiments build: A/B of the rule)
-    if (no32w && d.oW == 32 && d.Cin0 + d.Cin1 > 64) return false;
     SdcConvDesc e = d;
     e.precision = 3;
-    if (!wg2_ok(e, small, rowhalo)) return false;
+    if (!wg2_ok(e, small)) return false;
     const int rp = W3S_TILES / (d.oW / 2);
     const bool nores = d.rs[0] == 0 && d.rs[1] == 0 && d.rs[2] == 0 && d.rs[3] == 0 && d.rs[4] == 0;
     const int64_t tiles = (int64_t)d.B * (d.oD / 2) * (d.oH / 2) * (d.oW / 2);
@@ -1169,10 +1167,10 @@ bool wg3s_ok(const SdcConvDesc& d, bool small, bool rowhalo) {
 
 // F(2x2,3x3) with two workgroups per CU (sdc_conv_wino2s.inc): what conv_wg2_kernel takes with kD = 1 at rows of 128 / 64 / 32, whole
 // 64-channel output tiles, whole 4-channel stages in pairs, no fused residual; rows of 32: two row pairs of one plane per workgroup
-bool wg2s_ok(const SdcConvDesc& d, bool small, bool rowhalo) {
+bool wg2s_ok(const SdcConvDesc& d, bool small) {
     auto even = [](const int64_t* st) { return st[4] == 1 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0 && st[3] % 2 == 0; };
     if (!(d.precision >= 3 && d.kD == 1 && d.Cout % W2_BM == 0 && (d.oW == 128 || d.oW == 64 || d.oW == 32))) return false;
-    if (!wg2_ok(d, small, rowhalo)) return false;
+    if (!wg2_ok(d, small)) return false;
     const bool nores = d.rs[0] == 0 && d.rs[1] == 0 && d.rs[2] == 0 && d.rs[3] == 0 && d.rs[4] == 0;
     const int64_t tiles = (int64_t)d.B * d.oD * (d.oH / 2) * (d.oW / 2);
     return (d.oW != 32 || (d.oH / 2) % 2 == 0) && even(d.ys) && nores && (d.Cin1 == 0 || d.x1s[1] == d.x0s[1]) &&

@@ -133,10 +133,38 @@ def f16_tail(t, flip=False):
     return w.half().reshape(-1).view(torch.float32)
 
 
-def f16_floats(nw4, k, cin, cout):
-    """length in floats of a precision-6 buffer whose precision-4 prefix holds nw4 floats (covered taps k)"""
-    kc = f16_kc(k)
-    return (nw4 + 3) // 4 * 4 + k[0] * k[1] * k[2] * ((cin + kc - 1) // kc) * kc * cout // 2
+def conv_precision(n, k, cin, cout, f16=None, train=False):
+    """SdcConvDesc.precision for a packed conv weight of n floats (sizes: sdc_pack_conv_weight_floats): the lowest fp32 layout code
+    0, 2, 3, 4, 5 whose size matches -- a 1x1x3 buffer packed at 2, 3 or 4 reads as 2, a 3x3 one packed at 3 or 4 as 3 (the same
+    buffer).  f16 = 6 / 7: a sampler plan at that precision claims the buffers that carry precision 6's fp16 tail; with train, the
+    fine-tuning step's precision-8 buffer (grad_ops.pack_conv_weight), every one of which reads at f16."""
+    floats = functools.partial(_lib.get_lib().sdc_pack_conv_weight_floats, cout, cin, *k)
+    if train:
+        assert f16 in (6, 7) and n == floats(8), (f16, n, k, cin, cout)
+        return f16
+    if f16 in (6, 7) and f16_kc(k) > 0 and n == floats(6):
+        return f16
+    code = next((p for p in (0, 2, 3, 4, 5) if n == floats(p)), None)
+    assert code is not None, (n, k, cin, cout)
+    return code
+
+
+def conv_desc(x, x1, out, residual, cout, k, stride, pad, up, up_mode, precision):
+    """SdcConvDesc of a conv of the 5-D views x (and x1, channel-concatenated) into out (include/sdc.h), strides from the views"""
+    d = SdcConvDesc()
+    d.B, d.Cin0, d.iD, d.iH, d.iW = x.shape
+    d.Cin1, d.Cout = (0 if x1 is None else x1.shape[1]), cout
+    d.oD, d.oH, d.oW = out.shape[2:]
+    d.kD, d.kH, d.kW = k
+    d.sD, d.sH, d.sW = stride
+    d.pD, d.pH, d.pW = pad
+    d.uD, d.uH, d.uW = up
+    d.up_mode, d.precision = up_mode, precision
+    d.x0s[:] = _s5(x)
+    d.x1s[:] = _s5(x1) if x1 is not None else (0,) * 5
+    d.ys[:] = _s5(out)
+    d.rs[:] = _s5(residual) if residual is not None else (0,) * 5
+    return d
 
 
 class Pool:
@@ -254,29 +282,8 @@ class Plan:
             # library validates it
             assert tuple(out.shape[:2]) == (B, cout) and out.dim() == 5, (out.shape, (B, cout, *o))
             o = tuple(out.shape[2:])
-        nw = k[0] * k[1] * k[2] * (c0 + c1) * cout
-        wino = wp.dim() == 1 and k[2] == 3 and wp.numel() == nw + nw // 3 * 4
-        wino43 = wp.dim() == 1 and tuple(k) == (1, 1, 3) and wp.numel() == nw + nw // 3 * 4 + nw // 3 * 6   # precision 5: + F(4,3) taps
-        wino2 = wp.dim() == 1 and k[1] == 3 and k[2] == 3 and wp.numel() == nw + nw // 3 * 4 + nw // 9 * 16
-        wino3 = wp.dim() == 1 and tuple(k) == (3, 3, 3) and wp.numel() == nw + nw // 3 * 4 + nw // 9 * 16 + nw // 27 * 64
-        n4 = nw + (nw // 3 * 4 if k[2] == 3 else 0) + (nw // 9 * 16 if k[1] == 3 and k[2] == 3 else 0) + (nw // 27 * 64 if tuple(k) == (3, 3, 3) else 0)
-        f16 = self.precision in (6, 7) and wp.dim() == 1 and f16_kc(k) > 0 and wp.numel() == f16_floats(n4, tuple(k), c0 + c1, cout)   # precision 6: + fp16 tail
-        if f16:
-            wino = wino2 = wino3 = wino43 = False
-        assert f16 or wino or wino2 or wino3 or wino43 or wp.numel() == nw, (wp.shape, k, c0, c1, cout)
-        d = SdcConvDesc()
-        d.B, d.Cin0, d.Cin1, d.Cout = B, c0, c1, cout
-        d.iD, d.iH, d.iW = iD, iH, iW
-        d.oD, d.oH, d.oW = o
-        d.kD, d.kH, d.kW = k
-        d.sD, d.sH, d.sW = stride
-        d.pD, d.pH, d.pW = pad
-        d.uD, d.uH, d.uW = up
-        d.up_mode, d.precision = up_mode, (self.precision if f16 else 5 if wino43 else 4 if wino3 else 3 if wino2 else 2 if wino else 0)
-        d.x0s[:] = _s5(x)
-        d.x1s[:] = _s5(x1) if x1 is not None else (0,) * 5
-        d.ys[:] = _s5(out)
-        d.rs[:] = _s5(residual) if residual is not None else (0,) * 5
+        prec = conv_precision(wp.numel(), k, c0 + c1, cout, f16=self.precision)
+        d = conv_desc(x, x1, out, residual, cout, k, stride, pad, up, up_mode, prec)
         if residual is not None:
             assert tuple(residual.shape) == tuple(out.shape)
         self.keep += [d, x, x1, wp, bias, residual, out]     # the call list holds raw pointers only

@@ -1043,3 +1043,42 @@ def test_conv_wg2s_dispatch_is_pinned_and_matches_fp64(plan_cls, case):
     if y is not None:
         refn = F.silu(F.group_norm(ref, G, gam.double(), bet.double(), 1e-5))
         torch.testing.assert_close(y.cpu().reshape(ref.shape).double(), refn, rtol=1e-4, atol=2e-5)
+
+
+def test_conv_gn_refuses_a_kernel_gnparts_did_not_promise():
+    """sdc_conv_gn writes sdc_conv_gnparts(d, G) partial sums, and gnparts sees the descriptor only (16-byte aligned operands, no
+    residual).  This 3x3 conv runs conv_wg2s_kernel there (16 parts); with y one float into its buffer it runs conv_wg2_kernel
+    (8 parts), so the call is refused on the host, before any launch, naming the misaligned y.  Into an aligned view the same
+    call takes the fused path and matches sdc_conv + sdc_gn_stats."""
+    from safediffcon_amd import _lib
+    from safediffcon_amd.engine import as5, conv_desc, pack_conv_weight
+    lib = _lib.get_lib()
+    B, cin, cout, H, W, G = 2, 64, 64, 16, 128, 8
+    x = as5(det_tensor((B, cin, H, W), 211).to(DEV))
+    wp = pack_conv_weight(det_tensor((cout, cin, 3, 3), 212, 0.2).to(DEV), "conv", 3)
+    b = det_tensor((cout,), 213, 0.1).to(DEV)
+    n = B * cout * H * W
+    buf = torch.zeros(n + 4, device=DEV)
+    aligned, odd = buf[4:].view(B, cout, 1, H, W), buf[1:n + 1].view(B, cout, 1, H, W)
+    desc = lambda out: conv_desc(x, None, out, None, cout, (1, 3, 3), (1, 1, 1), (0, 1, 1), (1, 1, 1), 0, 3)  # noqa: E731
+    d = desc(aligned)
+    name = C.create_string_buffer(128)
+    assert lib.sdc_conv_describe(C.byref(d), name, 128, None) == 0 and name.value == b"conv_wg2s_kernel<128>"
+    nparts = int(lib.sdc_conv_gnparts(C.byref(d), G))
+    assert nparts == 16
+    parts = torch.zeros(B * G * nparts * 2, dtype=torch.float64, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    with pytest.raises(_lib.SdcError, match=r"y is not 8-byte aligned.*conv_wg2_kernel<128> with 8 partial sums"):
+        _lib.check(lib.sdc_conv_gn(C.byref(desc(odd)), x.data_ptr(), None, wp.data_ptr(), b.data_ptr(), None, odd.data_ptr(),
+                                   parts.data_ptr(), G, stream), "sdc_conv_gn")
+    _lib.check(lib.sdc_conv_gn(C.byref(d), x.data_ptr(), None, wp.data_ptr(), b.data_ptr(), None, aligned.data_ptr(),
+                               parts.data_ptr(), G, stream), "sdc_conv_gn")
+    nst = (int(lib.sdc_gn_stats_bytes(B, G)) + 3) // 4
+    st, st_ref = torch.empty(nst, device=DEV), torch.empty(nst, device=DEV)
+    _lib.check(lib.sdc_gn_finalize(parts.data_ptr(), st.data_ptr(), B, G, nparts, (cout // G) * H * W, 1e-5, stream), "sdc_gn_finalize")
+    ref = torch.empty_like(aligned)
+    _lib.check(lib.sdc_conv(C.byref(desc(ref)), x.data_ptr(), None, wp.data_ptr(), b.data_ptr(), None, ref.data_ptr(), stream), "sdc_conv")
+    _lib.check(lib.sdc_gn_stats(ref.data_ptr(), st_ref.data_ptr(), B, cout, G, H * W, 1e-5, stream), "sdc_gn_stats")
+    torch.cuda.synchronize()
+    assert torch.equal(aligned, ref)
+    torch.testing.assert_close(st[:2 * B * G], st_ref[:2 * B * G], rtol=1e-5, atol=1e-6)

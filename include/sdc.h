@@ -288,9 +288,14 @@ typedef struct SdcStepDesc {
 /* gpar: device float[8] of guidance constants (kept on the device so a captured graph survives a new
  * conformal quantile Q):  burgers {w_score, u_bound^2, Q, 10}; tokamak {w_obj, w_safe, guidance_scaler,
  * safety_threshold, Q}; smoke {w_safe, safe_bound, Q, standard_fixed_ratio}.
- * sdc_guide_reduce: per-sample hinge-active flag + arg-extremum of the safety functional evaluated on
- * x0 = a x - b eps  -> gscal[4*B] = {active, arg, extremum, 1/ties}   (1D/utils/guidance.py:58-77, tokamak/utils/guidance.py:32-56,
- * tokamak/utils/metrics.py:144-151, 2d/inference_2d.py:173-186). */
+ * sdc_guide_reduce: per-sample hinge derivative + arg-extremum of the safety functional evaluated on
+ * x0 = a x - b eps (clipped to [-1, 1] when ddim)  -> gscal[4*B] = {active, arg, extremum, 1/ties}
+ * (1D/utils/guidance.py:58-77, tokamak/utils/guidance.py:32-56, tokamak/utils/metrics.py:144-151, 2d/inference_2d.py:173-186).
+ *   active   = d/ds max(s, 0) at the hinge argument s: 1 for s > 0, 0 for s < 0 and 1/2 at s == 0 exactly (what the
+ *              backward of torch.maximum(s, 0) passes at a tie)
+ *   arg      = flat per-sample index of the first element attaining the amax / amin (int bits), 0 in the mean modes
+ *   extremum = that amax / amin value ; 1/ties = one over the number of elements attaining it (amax / amin backward
+ *              splits the gradient evenly between tied elements) */
 int sdc_guide_reduce(const SdcStepDesc* d, const float* x, const float* eps, const float* coef, const int32_t* t_dev,
                      const float* gpar, float* gscal, void* stream);
 /* guide: 0 none | 1 built-in closed-form gradient (needs gpar, gscal[, target]) | 2 external gradient tensor gext
@@ -299,7 +304,9 @@ int sdc_step_update(const SdcStepDesc* d, const float* x, const float* eps, cons
                     const int32_t* t_dev, const int32_t* draw_dev, const float* noise, int64_t noise_stride,
                     const float* gpar, const float* gscal, const float* target, const float* c0, const float* c1,
                     const float* c2, float* xout, float* x0out, void* stream);
-/* conditioning writes only (initial x_T) */
+/* conditioning writes only (initial x_T).  Validates like sdc_step_update with impose set, before any launch: c0 always;
+ * c1 unless the model is smoke (SDC_ENULL); the tensor behind has_wgt (burgers/tokamak c2, smoke c1; SDC_ENULL);
+ * d->impose == 2 (control channels only) for smoke alone (SDC_EINVAL). */
 int sdc_impose(const SdcStepDesc* d, float* x, const float* c0, const float* c1, const float* c2, void* stream);
 /* x = N(0,1) from the same Philox stream (draw index *draw_dev), then (*draw_dev)++ handled by sdc_advance */
 int sdc_randn(float* x, int64_t n, uint64_t seed, const int32_t* draw_dev, void* stream);

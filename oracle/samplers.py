@@ -40,22 +40,99 @@ class _Draws:
         return z
 
 
-def _posterior_step(tabs, x, t, eps, g, k, clip, z):
+def ddpm_row(tabs, t, k=1.0):
+    """Coefficient row of DDPM timestep t: {a, b, c1, c2, sigma, k} (sigma = exp(0.5 * posterior_log_variance_clipped))."""
+    return dict(a=tabs["sqrt_recip_alphas_cumprod"][t], b=tabs["sqrt_recipm1_alphas_cumprod"][t],
+                c1=tabs["posterior_mean_coef1"][t], c2=tabs["posterior_mean_coef2"][t],
+                sigma=(0.5 * tabs["posterior_log_variance_clipped"][t]).exp(), k=k)
+
+
+def ddim_row(tabs, time, time_next, eta, k=1.0):
+    """Coefficient row of one DDIM step: {a, b, c1 = sqrt(alpha_next), c2 = c, sigma, k, last} (1D/model/diffusion.py:500-504)."""
+    row = dict(a=tabs["sqrt_recip_alphas_cumprod"][time], b=tabs["sqrt_recipm1_alphas_cumprod"][time], k=k,
+               last=time_next < 0)
+    if time_next >= 0:
+        alpha, alpha_next = tabs["alphas_cumprod"][time], tabs["alphas_cumprod"][time_next]
+        sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
+        row.update(c1=alpha_next.sqrt(), c2=(1 - alpha_next - sigma ** 2).sqrt(), sigma=sigma)
+    return row
+
+
+def _posterior_row(row, x, eps, g, clip, z):
     """eps -> x0 -> eps' = eps + k*g -> x0' -> clamp -> posterior mean -> + sigma z."""
-    a, b = tabs["sqrt_recip_alphas_cumprod"][t], tabs["sqrt_recipm1_alphas_cumprod"][t]
     if g is not None:
-        eps = eps + g * k
-    x0 = a * x - b * eps
+        eps = eps + g * row["k"]
+    x0 = row["a"] * x - row["b"] * eps
     if clip:
         x0 = x0.clamp(-1.0, 1.0)
-    mean = tabs["posterior_mean_coef1"][t] * x0 + tabs["posterior_mean_coef2"][t] * x
+    mean = row["c1"] * x0 + row["c2"] * x
     if z is None:
         return mean, x0
-    return mean + (0.5 * tabs["posterior_log_variance_clipped"][t]).exp() * z, x0
+    return mean + row["sigma"] * z, x0
+
+
+def _x0_row(row, x, eps):
+    return row["a"] * x - row["b"] * eps
+
+
+def _posterior_step(tabs, x, t, eps, g, k, clip, z):
+    """_posterior_row at DDPM timestep t of the tables (bench.py's CPU baseline steps with it)."""
+    return _posterior_row(ddpm_row(tabs, t, k), x, eps, g, clip, z)
 
 
 def _x0_from_eps(tabs, x, t, eps):
-    return tabs["sqrt_recip_alphas_cumprod"][t] * x - tabs["sqrt_recipm1_alphas_cumprod"][t] * eps
+    return _x0_row(ddpm_row(tabs, t), x, eps)
+
+
+# ----------------------------------------------------------------------------
+# one reverse step (the bodies of the loops below; any float dtype: the row may hold 0-d tensors or Python floats)
+#   x, eps   state and predicted noise
+#   row      ddpm_row / ddim_row (or the same keys filled by the caller)
+#   z        the step's normal draw, None where the loop makes none (t == 0)
+#   guide    x0 -> dJ/dx0 (autograd of the restated J) or None
+#   impose   closure writing the conditions into its argument in place, or None
+# each returns (x_next, x0): x0 is the guided, clipped x_start the update was formed from
+# ----------------------------------------------------------------------------
+
+def ddpm_step(x, eps, row, z, guide, impose, *, clip=True):
+    """p_sample with guidance on x0 (guidance_u0): 1D/model/diffusion.py:226-306, 2d/ddpm/diffusion_2d.py:242-285."""
+    g = guide(_x0_row(row, x, eps)) if guide is not None else None
+    out, x0 = _posterior_row(row, x, eps, g, clip, z)
+    if impose is not None:
+        impose(out)
+    return out, x0
+
+
+def ddpm_calib_step(x, eps, row, z, guide, impose, *, clip=True):
+    """The calibration branch (guidance_u0 False, 1D/model/diffusion.py:421-447): p_sample twice, the first result only
+    feeds nabla_J(img_curr).  z = (discarded draw, used draw) or None."""
+    z0, z1 = z if z is not None else (None, None)
+    cur, _ = _posterior_row(row, x, eps, None, clip, z0)
+    eps2 = eps + (guide(cur) * row["k"] if guide is not None else 0)
+    out, x0 = _posterior_row(row, x, eps2, None, clip, z1)
+    if impose is not None:
+        impose(out)
+    return out, x0
+
+
+def ddim_step(x, eps, row, z, guide, impose):
+    """One ddim_sample step with model_predictions(clip_x_start=True, rederive_pred_noise=True): x0 clipped, guidance
+    evaluated on the clipped x0, eps re-derived from the clipped guided x0; the last step returns x0 itself."""
+    a, b = row["a"], row["b"]
+    x0 = (a * x - b * eps).clamp(-1.0, 1.0)
+    if guide is not None:
+        eps = eps + guide(x0) * row["k"]
+    x0 = (a * x - b * eps).clamp(-1.0, 1.0)
+    eps = (a * x - x0) / b
+    if row["last"]:
+        out = x0.clone()
+    else:
+        out = x0 * row["c1"] + row["c2"] * eps
+        if z is not None:
+            out = out + row["sigma"] * z
+    if impose is not None:
+        impose(out)
+    return out, x0
 
 
 # ----------------------------------------------------------------------------
@@ -115,35 +192,8 @@ def smoke_guidance(Q, w_safe, safe_bound):
 # reverse loops
 # ----------------------------------------------------------------------------
 
-def _lucid_loop(eps_fn, tabs, shape, noise, impose, *, nablaJ, J_scheduler, guidance_u0,
-                clip_denoised, enable_grad, T):
-    """Common body of the burgers / tokamak p_sample_loop."""
-    draw = _Draws(noise)
-    img = draw().clone()
-    for t in reversed(range(T)):
-        impose(img)
-        eps = eps_fn(img, torch.full((shape[0],), t, dtype=torch.long))
-        k = J_scheduler(t) if J_scheduler is not None else 1.0
-        if guidance_u0:
-            g = nablaJ(_x0_from_eps(tabs, img, t, eps)) if nablaJ is not None else None
-            img, _ = _posterior_step(tabs, img, t, eps, g, k, clip_denoised, draw() if t > 0 else None)
-        else:
-            # calibration branch: p_sample twice; first result only feeds nabla_J(img_curr)
-            cur, _ = _posterior_step(tabs, img, t, eps, None, k, clip_denoised, draw() if t > 0 else None)
-            eps2 = eps + (nablaJ(cur) * k if nablaJ is not None else 0)
-            _ = eps_fn(img, torch.full((shape[0],), t, dtype=torch.long))   # discarded forward (:423)
-            nxt, _ = _posterior_step(tabs, img, t, eps2, None, k, clip_denoised, draw() if t > 0 else None)
-            if t != 0 or not enable_grad:
-                img = nxt
-            # t == 0 with enable_grad and guidance_u0 False: reference keeps img (:445-447)
-    return img
-
-
-def sample_burgers(eps_fn, tabs, batch, noise, *, u_init, u_final, nablaJ=None, J_scheduler=None,
-                   guidance_u0=True, w_groundtruth=None, clip_denoised=True, enable_grad=True,
-                   condition_idx=10, train_on_padded_locations=False, shape=(3, 16, 128), T=None):
-    T = T or tabs["betas"].shape[0]
-
+def burgers_impose(u_init, u_final, w_groundtruth=None, condition_idx=10, train_on_padded_locations=False):
+    """set_condition / set_pad_condition, 1D/model/diffusion.py:336-366,380-394 (in place)."""
     def impose(img):
         img[:, 0, 0, :] = u_init
         img[:, 0, condition_idx, :] = u_final
@@ -153,7 +203,60 @@ def sample_burgers(eps_fn, tabs, batch, noise, *, u_init, u_final, nablaJ=None, 
             img[:, 0, condition_idx + 1:, :] = 0
             img[:, 1, condition_idx:, :] = 0
             img[:, 2, condition_idx:, :] = 0
+    return impose
 
+
+def tokamak_impose(u_init, u_final, nt=122, train_on_padded_locations=True, w_groundtruth=None):
+    """tokamak/model/diffusion.py:295-308,330-336; w_groundtruth as the DDIM path writes it (:411,:453)."""
+    def impose(img):
+        img[:, :3, 0] = u_init
+        img[:, [0, 2], :nt] = u_final
+        if not train_on_padded_locations:
+            img[:, :3, nt:] = 0
+            img[:, 3:, nt - 1:] = 0
+        if w_groundtruth is not None:
+            img[:, 3:, :] = w_groundtruth
+    return impose
+
+
+def smoke_impose(init, control=None, control_only=False):
+    """2d/ddpm/diffusion_2d.py:297-301,310-312; control_only: what follows the DDIM loop (:400-401)."""
+    def impose(x):
+        if not control_only:
+            x[:, 0, 0] = init
+        if control is not None:
+            x[:, :, 3:5] = control
+    return impose
+
+
+def _lucid_loop(eps_fn, tabs, shape, noise, impose, *, nablaJ, J_scheduler, guidance_u0,
+                clip_denoised, enable_grad, T):
+    """Common body of the burgers / tokamak p_sample_loop."""
+    draw = _Draws(noise)
+    img = draw().clone()
+    impose(img)
+    for t in reversed(range(T)):
+        eps = eps_fn(img, torch.full((shape[0],), t, dtype=torch.long))
+        row = ddpm_row(tabs, t, J_scheduler(t) if J_scheduler is not None else 1.0)
+        nxt_impose = impose if t > 0 else None                           # the loop imposes before every forward only
+        if guidance_u0:
+            img, _ = ddpm_step(img, eps, row, draw() if t > 0 else None, nablaJ, nxt_impose, clip=clip_denoised)
+        else:
+            z = (draw(), draw()) if t > 0 else None
+            _ = eps_fn(img, torch.full((shape[0],), t, dtype=torch.long))   # discarded forward (:423)
+            keep = t == 0 and enable_grad                                # reference keeps img there (:445-447)
+            nxt, _ = ddpm_calib_step(img, eps, row, z, nablaJ, None if keep else nxt_impose, clip=clip_denoised)
+            if not keep:
+                img = nxt
+    return img
+
+
+def sample_burgers(eps_fn, tabs, batch, noise, *, u_init, u_final, nablaJ=None, J_scheduler=None,
+                   guidance_u0=True, w_groundtruth=None, clip_denoised=True, enable_grad=True,
+                   condition_idx=10, train_on_padded_locations=False, shape=(3, 16, 128), T=None):
+    T = T or tabs["betas"].shape[0]
+
+    impose = burgers_impose(u_init, u_final, w_groundtruth, condition_idx, train_on_padded_locations)
     return _lucid_loop(eps_fn, tabs, (batch, *shape), noise, impose, nablaJ=nablaJ, J_scheduler=J_scheduler,
                        guidance_u0=guidance_u0, clip_denoised=clip_denoised, enable_grad=enable_grad, T=T)
 
@@ -166,13 +269,7 @@ def sample_tokamak(eps_fn, tabs, batch, noise, *, u_init, u_final, nablaJ=None, 
         # reference bug: ``img[:,1,:,:] = w_groundtruth`` on a 3-D tensor
         raise IndexError("too many indices for tensor of dimension 3")
 
-    def impose(img):
-        img[:, :3, 0] = u_init
-        img[:, [0, 2], :nt] = u_final
-        if not train_on_padded_locations:
-            img[:, :3, nt:] = 0
-            img[:, 3:, nt - 1:] = 0
-
+    impose = tokamak_impose(u_init, u_final, nt, train_on_padded_locations)
     return _lucid_loop(eps_fn, tabs, (batch, *shape), noise, impose, nablaJ=nablaJ, J_scheduler=J_scheduler,
                        guidance_u0=guidance_u0, clip_denoised=clip_denoised, enable_grad=enable_grad, T=T)
 
@@ -183,17 +280,11 @@ def sample_smoke(eps_fn, tabs, batch, noise, *, init, control=None, design_fn=No
     draw = _Draws(noise)
     x = draw().clone()
 
-    def impose(x):
-        x[:, 0, 0] = init
-        if control is not None:
-            x[:, :, 3:5] = control
-
+    impose = smoke_impose(init, control)
     impose(x)
     for t in reversed(range(T)):
         eps = eps_fn(x, torch.full((batch,), t, dtype=torch.long))
-        g = design_fn(_x0_from_eps(tabs, x, t, eps)) if design_fn is not None else None
-        x, _ = _posterior_step(tabs, x, t, eps, g, ratio, True, draw() if t > 0 else None)
-        impose(x)
+        x, _ = ddpm_step(x, eps, ddpm_row(tabs, t, ratio), draw() if t > 0 else None, design_fn, impose, clip=True)
     return x
 
 
@@ -275,41 +366,21 @@ def _ddim_loop(eps_fn, tabs, shape, noise, impose, finish, *, S, eta, guide, k_o
     model_predictions(clip_x_start=True, rederive_pred_noise=True): x0 clipped, guidance evaluated on the clipped x0,
     eps re-derived from the clipped guided x0."""
     T = tabs["betas"].shape[0]
-    ac = tabs["alphas_cumprod"]
     draw = _Draws(noise)
     img = draw().clone()
     impose(img)
     for time, time_next in ddim_pairs(T, S):
-        a, b = tabs["sqrt_recip_alphas_cumprod"][time], tabs["sqrt_recipm1_alphas_cumprod"][time]
         eps = eps_fn(img, torch.full((shape[0],), time, dtype=torch.long))
-        x0 = (a * img - b * eps).clamp(-1.0, 1.0)
-        if guide is not None:
-            eps = eps + guide(x0) * k_of_t(time)
-        x0 = (a * img - b * eps).clamp(-1.0, 1.0)
-        eps = (a * img - x0) / b
-        if time_next < 0:
-            img = x0
-            continue
-        alpha, alpha_next = ac[time], ac[time_next]
-        sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
-        c = (1 - alpha_next - sigma ** 2).sqrt()
-        img = x0 * alpha_next.sqrt() + c * eps + sigma * draw()
-        impose(img)
+        row = ddim_row(tabs, time, time_next, eta, k_of_t(time))
+        last = time_next < 0
+        img, _ = ddim_step(img, eps, row, None if last else draw(), guide, None if last else impose)
     finish(img)
     return img
 
 
 def ddim_burgers(eps_fn, tabs, batch, noise, *, S, eta, u_init, u_final, nablaJ=None, J_scheduler=None, guidance_u0=True,
                  w_groundtruth=None, condition_idx=10, train_on_padded_locations=False, shape=(3, 16, 128)):
-    def impose(img):
-        img[:, 0, 0, :] = u_init
-        img[:, 0, condition_idx, :] = u_final
-        if w_groundtruth is not None:
-            img[:, 1, :, :] = w_groundtruth
-        if not train_on_padded_locations:
-            img[:, 0, condition_idx + 1:, :] = 0
-            img[:, 1, condition_idx:, :] = 0
-            img[:, 2, condition_idx:, :] = 0
+    impose = burgers_impose(u_init, u_final, w_groundtruth, condition_idx, train_on_padded_locations)
     k = (lambda t: J_scheduler(t)) if J_scheduler is not None else (lambda t: 1.0)
     return _ddim_loop(eps_fn, tabs, (batch, *shape), noise, impose, lambda img: None, S=S, eta=eta,
                       guide=nablaJ if guidance_u0 else None, k_of_t=k)
@@ -317,27 +388,13 @@ def ddim_burgers(eps_fn, tabs, batch, noise, *, S, eta, u_init, u_final, nablaJ=
 
 def ddim_tokamak(eps_fn, tabs, batch, noise, *, S, eta, u_init, u_final, nablaJ=None, J_scheduler=None, guidance_u0=True,
                  w_groundtruth=None, nt=122, train_on_padded_locations=True, shape=(12, 128)):
-    def impose(img):
-        img[:, :3, 0] = u_init
-        img[:, [0, 2], :nt] = u_final
-        if not train_on_padded_locations:
-            img[:, :3, nt:] = 0
-            img[:, 3:, nt - 1:] = 0
-        if w_groundtruth is not None:
-            img[:, 3:, :] = w_groundtruth                                 # the DDIM path indexes correctly (:411,:453)
+    impose = tokamak_impose(u_init, u_final, nt, train_on_padded_locations, w_groundtruth)   # the DDIM path indexes correctly
     k = (lambda t: J_scheduler(t)) if J_scheduler is not None else (lambda t: 1.0)
     return _ddim_loop(eps_fn, tabs, (batch, *shape), noise, impose, lambda img: None, S=S, eta=eta,
                       guide=nablaJ if guidance_u0 else None, k_of_t=k)
 
 
 def ddim_smoke(eps_fn, tabs, batch, noise, *, S, eta, init, control=None, design_fn=None, ratio=1.0, shape=(32, 7, 64, 64)):
-    def impose(x):
-        x[:, 0, 0] = init
-        if control is not None:
-            x[:, :, 3:5] = control
-
-    def finish(x):                                                        # 2d/ddpm/diffusion_2d.py:400-401
-        if control is not None:
-            x[:, :, 3:5] = control
+    impose, finish = smoke_impose(init, control), smoke_impose(init, control, control_only=True)
     return _ddim_loop(eps_fn, tabs, (batch, *shape), noise, impose, finish, S=S, eta=eta, guide=design_fn,
                       k_of_t=lambda t: ratio)

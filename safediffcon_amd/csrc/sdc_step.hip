@@ -8,7 +8,8 @@
 //   burgers: {w_score, u_bound^2, Q, SCALER=10}
 //   tokamak: {w_obj, w_safe, guidance_scaler, safety_threshold, Q}
 //   smoke  : {w_safe, safe_bound, Q, standard_fixed_ratio}
-// gscal (device float[4*B]) = {hinge-active flag, arg-extremum flat index, extremum, 1/ties} from sdc_guide_reduce.
+// gscal (device float[4*B]) = {hinge derivative (1, 0, or 1/2 at exact equality), arg-extremum flat index, extremum, 1/ties}
+// from sdc_guide_reduce.
 #include "sdc_common.h"
 
 namespace {
@@ -86,6 +87,11 @@ __device__ __forceinline__ Coef load_coef(const float* coef, const int32_t* t_de
     return Coef{c[0], c[1], c[2], c[3], c[4], c[5], c[6]};
 }
 
+// x0 = a x - b eps with its two roundings spelled out.  guide_grad's tie path compares the x0 the update kernel recomputes
+// with the extremum the reduce kernel stored; left as `a * x - b * e`, the compiler may contract one kernel's expression into
+// fma(a, x, -(b e)) and the other's into fma(-b, e, a x), which differ in the last bit and lose the tied elements' gradient.
+__device__ __forceinline__ float x0_of(const Coef& c, float x, float e) { return __fmaf_rn(c.a, x, -__fmul_rn(c.b, e)); }
+
 // safety functional f(state) per sample, evaluated on v(idx) (a callable giving the element value)
 //   burgers: 10 * mean|amax over (c=2, h<11)      (1D/utils/guidance.py:66-70)
 //   tokamak: min_t<nt 7*x[1,t]                    (tokamak/utils/metrics.py:144-151)
@@ -160,11 +166,13 @@ __global__ __launch_bounds__(NT) void guide_reduce_kernel(const SdcStepDesc d, c
     float f, raw; int arg, ties;
     const bool ddim = d.ddim != 0;
     safety_functional(d, [&](int i) {
-        const float v = c.a * xb[i] - c.b * eb[i];
+        const float v = x0_of(c, xb[i], eb[i]);
         return ddim ? fminf(fmaxf(v, -1.0f), 1.0f) : v;
     }, shf, shi, f, arg, ties, raw);
     if (threadIdx.x == 0) {
-        gscal[b * 4] = hinge_arg(d, gpar, f) > 0.f ? 1.0f : 0.0f;
+        // d/ds max(s, 0): 1 above the hinge, 0 below, and 1/2 at exact equality (torch.maximum's backward splits it)
+        const float h = hinge_arg(d, gpar, f);
+        gscal[b * 4] = h > 0.f ? 1.0f : (h == 0.f ? 0.5f : 0.0f);
         gscal[b * 4 + 1] = __int_as_float(arg);
         gscal[b * 4 + 2] = raw;                          // the extremum itself (for tie detection)
         gscal[b * 4 + 3] = 1.0f / (float)ties;
@@ -266,7 +274,7 @@ __global__ __launch_bounds__(NT) void step_update_kernel(const StepArgs a) {
             float q[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                q[j] = c.a * xs[j] - c.b * es[j];
+                q[j] = x0_of(c, xs[j], es[j]);
                 if (d.ddim) q[j] = fminf(fmaxf(q[j], -1.0f), 1.0f);
             }
             *reinterpret_cast<float4*>(a.x0out + e0) = make_float4(q[0], q[1], q[2], q[3]);
@@ -284,13 +292,13 @@ __global__ __launch_bounds__(NT) void step_update_kernel(const StepArgs a) {
             float e = es[j];
             const bool ddim = d.ddim != 0;
             if (d.guide == 1) {
-                float x0 = c.a * xs[j] - c.b * e;
+                float x0 = x0_of(c, xs[j], e);
                 if (ddim) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
                 e = e + guide_grad(d, a.gpar, a.gscal, a.target, b, i0 + j, x0) * c.k;
             } else if (d.guide == 2) {
                 e = e + gs[j] * c.k;
             }
-            float x0 = c.a * xs[j] - c.b * e;
+            float x0 = x0_of(c, xs[j], e);
             if (d.clip || ddim) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
             x0c[j] = x0;
             float o;
@@ -455,6 +463,9 @@ int sdc_step_update(const SdcStepDesc* d, const float* x, const float* eps, cons
 int sdc_impose(const SdcStepDesc* d, float* x, const float* c0, const float* c1, const float* c2, void* stream) {
     SDC_REQUIRE(d && x && c0, SDC_ENULL, "sdc_impose: null pointer");
     if (int rc = check_desc(*d, "sdc_impose")) return rc;
+    SDC_REQUIRE(d->model == SDC_MODEL_SMOKE || c1, SDC_ENULL, "sdc_impose: needs c1");
+    SDC_REQUIRE(!d->has_wgt || (d->model == SDC_MODEL_SMOKE ? c1 : c2), SDC_ENULL, "sdc_impose: has_wgt needs its tensor");
+    SDC_REQUIRE(d->impose != 2 || d->model == SDC_MODEL_SMOKE, SDC_EINVAL, "sdc_impose: impose=2 is smoke-only");
     const int64_t per = (int64_t)d->d0 * d->d1 * d->d2 * d->d3;
     const int64_t n = per * d->B;
     hipLaunchKernelGGL(impose_kernel, dim3(grid_for(n)), dim3(NT), 0, sdc::as_stream(stream), *d, x, c0, c1, c2, per, n);

@@ -390,6 +390,31 @@ int sdc_conv_wgrad_f16(const SdcWgradDesc* d, const float* g, const float* x, co
                        size_t work_bytes, void* stream);
 int sdc_conv_wgrad_describe(const SdcWgradDesc* d, char* name, size_t cap);
 
+/* The 7-tap stem convs with fp16 operands and fp32 accumulation (net.stem_f16, opt-in, samplers only; DESIGN.md section 13;
+ * csrc/sdc_conv_stem_f16.hip).  A switch of its own beside SdcConvDesc.precision: sdc_conv, its dispatch and every layout above are
+ * untouched; the caller asks sdc_conv_stem_f16_ok and, where it says 1, calls sdc_conv_stem_f16 on the stem's own fp16 buffer.
+ *
+ * sdc_conv_stem_f16_ok: 1 when conv_stem_f16_kernel covers the descriptor, else 0.  Host only, launches nothing, reads the
+ * descriptor alone and never keys on B (a sample's bits do not depend on its batch).  Covered: kW = 7 with (kD, kH) = (1, 1), (1, 7)
+ * or (7, 7); stride 1, no upsampling; pad 3 along every 7-tap axis and 0 along every 1-tap axis, output size = input size;
+ * Cin0 <= 8, Cin1 = 0; Cout % 64 == 0; rows of oW = 16, 32, 64 or 128 columns; dense input and output rows (x0s[4] == ys[4] == 1, every
+ * other stride free).  d->precision, d->x1s and d->rs are unread: no second input, no fused residual.
+ *
+ * Buffer layout (sdc_pack_stem_f16_bytes(...) bytes, 16-byte aligned; 0 for other taps or Cin > 8).  With NS = ceil(7 kH / 2):
+ *     Wh[kd][s][co][8 h + ci] = (fp16, RNE) w[co][ci][kd][kh][kw],   kh * 7 + kw = 2 s + h,   kd < kD, s < NS, h < 2, ci < 8,
+ * zero for ci >= Cin and for the one tap 2 s + h = 7 kH past the end: a 16-deep MFMA step s covers two adjacent taps of the
+ * (kh, kw) walk, eight channels each (kD * NS * Cout * 16 halves: 350 KB for the smoke stem, Cout 64).
+ * sdc_pack_stem_f16 writes it on the device from the nn.Conv weight w (Cout, Cin, kD, kH, kW), one launch on `stream`.
+ *
+ * sdc_conv_stem_f16: y = conv(x, w) + bias (bias may be null), asynchronous on `stream`.  SDC_ENULL for a null d, x, wh or y and
+ * SDC_EINVAL (with a message) for a descriptor sdc_conv_stem_f16_ok rejects, both before any launch; SDC_EALIGN for a misaligned wh.
+ * Rounding: fp16 x fp16 products are exact in fp32, so the result is an fp64 conv of the rounded operands up to fp32 summation
+ * order.  Fixed k order, no K split, no atomics: deterministic. */
+int sdc_conv_stem_f16_ok(const SdcConvDesc* d);
+size_t sdc_pack_stem_f16_bytes(int Cout, int Cin, int kD, int kH, int kW);
+int sdc_pack_stem_f16(const float* w, void* out, int Cout, int Cin, int kD, int kH, int kW, void* stream);
+int sdc_conv_stem_f16(const SdcConvDesc* d, const float* x, const void* wh, const float* bias, float* y, void* stream);
+
 /* Backward of sdc_gn_apply (GroupNorm -> (scale+1, shift) -> SiLU; Block, conv3d.py:189-204, 1D/model/unet.py:128-147):
  * h = the conv output the forward normalised (contiguous (B,C,S)), stats from the forward, ss = per-sample rows
  * [scale (C) | shift (C)] at ss + b*ss_b_stride or null.  rows: sdc_gn_silu_bwd_floats(B, C, G, S) floats, 8-byte aligned.  Writes

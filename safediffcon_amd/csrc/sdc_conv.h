@@ -102,4 +102,7 @@ const char* f16_name(const SdcConvDesc& d);
 int launch_f16(const ConvArgs& a, const _Float16* wh, hipStream_t s, const int32_t* gexp = nullptr);   // gexp: scaled (data-gradient) form
 int pack_f16_tail(const float* w, float* tail, int64_t gap, int Cout, int Cin, int kD, int kH, int kW, hipStream_t s);
 
+// defined in sdc_conv_stem_f16.hip (net.stem_f16)
+int launch_stem_f16(const SdcConvDesc& d, const float* x, const _Float16* wh, const float* bias, float* y, hipStream_t s);
+
 }  // namespace sdcconv

@@ -1840,6 +1840,21 @@ Route route(const SdcConvDesc& d, const Operands& op, int G, bool split) {
     return direct(4);
 }
 
+// net.stem_f16: coverage of conv_stem_f16_kernel (sdc_conv_stem_f16.hip), the fp16-operand form of the 7-tap stem convs.  Descriptor
+// only and keyed on per-sample sizes, never on B: the kernel a stem runs, and so a sample's bits, do not depend on its batch.  1x1x7,
+// 1x7x7 or 7x7x7 taps, stride 1, no upsampling, 'same' padding (3 along every 7-tap axis, 0 along the others), one input of at most 8
+// channels, whole 64-channel blocks of outputs, whole rows of 16 / 32 / 64 / 128 columns, dense input and output rows (every other
+// stride is free: the smoke net hands its state in as a frame-major view).  sdc_conv and route() never look at this: the caller
+// (Plan.conv with stem_f16) asks sdc_conv_stem_f16_ok and calls sdc_conv_stem_f16 on the stem's own fp16 buffer.
+bool stem_f16_ok(const SdcConvDesc& d) {
+    if (!(d.kW == 7 && ((d.kD == 1 && (d.kH == 1 || d.kH == 7)) || (d.kD == 7 && d.kH == 7)))) return false;
+    if (!(d.sD == 1 && d.sH == 1 && d.sW == 1 && d.uD == 1 && d.uH == 1 && d.uW == 1 && d.up_mode == 0)) return false;
+    if (!(d.pW == 3 && d.pH == d.kH / 2 && d.pD == d.kD / 2 && d.oD == d.iD && d.oH == d.iH && d.oW == d.iW)) return false;
+    if (!(d.B > 0 && d.oD > 0 && d.oH > 0 && d.Cin0 >= 1 && d.Cin0 <= 8 && d.Cin1 == 0 && d.Cout > 0 && d.Cout % 64 == 0)) return false;
+    if (!(d.oW == 16 || d.oW == 32 || d.oW == 64 || d.oW == 128)) return false;
+    return d.x0s[4] == 1 && d.ys[4] == 1;
+}
+
 // y (strided) = sum over the splits, in split order, of the dense partial copies of sdc_conv_splitk
 __global__ __launch_bounds__(256) void splitk_sum_kernel(const float* __restrict__ part, float* __restrict__ y, int S, int64_t elems, int C,
                                                          int oD, int oH, int oW, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
@@ -1935,6 +1950,18 @@ extern "C" int sdc_conv_describe(const SdcConvDesc* dp, char* name, size_t cap, 
     if (name && cap) { std::strncpy(name, r.name, cap - 1); name[cap - 1] = 0; }
     if (mfma_share) *mfma_share = r.share;
     return SDC_OK;
+}
+
+// net.stem_f16 (include/sdc.h): the covered 7-tap stem convs with fp16 operands and fp32 accumulation, on their own fp16 buffer
+extern "C" int sdc_conv_stem_f16_ok(const SdcConvDesc* dp) {
+    return dp && stem_f16_ok(*dp) ? 1 : 0;
+}
+
+extern "C" int sdc_conv_stem_f16(const SdcConvDesc* dp, const float* x, const void* wh, const float* bias, float* y, void* stream) {
+    SDC_REQUIRE(dp && x && wh && y, SDC_ENULL, "sdc_conv_stem_f16: null pointer");
+    SDC_REQUIRE(stem_f16_ok(*dp), SDC_EINVAL, "sdc_conv_stem_f16: descriptor not covered (sdc_conv_stem_f16_ok returned 0): %dx%dx%d taps, Cin %d+%d, "
+                "Cout %d, rows of %d", dp->kD, dp->kH, dp->kW, dp->Cin0, dp->Cin1, dp->Cout, dp->oW);
+    return launch_stem_f16(*dp, x, reinterpret_cast<const _Float16*>(wh), bias, y, sdc::as_stream(stream));
 }
 
 namespace {

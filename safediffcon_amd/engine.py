@@ -133,6 +133,21 @@ def f16_tail(t, flip=False):
     return w.half().reshape(-1).view(torch.float32)
 
 
+def pack_stem_f16(w):
+    """fp16 buffer of a 7-tap stem conv weight (Cout, Cin <= 8, *k) with k = 1x1x7, 1x7x7 or 7x7x7 for sdc_conv_stem_f16 (include/sdc.h;
+    host twin of sdc_pack_stem_f16, bit for bit): Wh[kd][s][co][8 h + ci] = w[co][ci][kd][tap = kh * 7 + kw = 2 s + h] rounded to fp16
+    (RNE), NS = ceil(7 kH / 2) steps s, zero for ci >= Cin and for the one tap past the end; returned as the float32 words that hold it"""
+    t5 = as5(w).to(torch.float32)
+    co, ci, kD, kH, kW = t5.shape
+    if not (kW == 7 and (kD, kH) in ((1, 1), (1, 7), (7, 7)) and 1 <= ci <= 8):
+        raise ValueError(f"pack_stem_f16: taps 1x1x7, 1x7x7 or 7x7x7 and Cin <= 8 (got {tuple(t5.shape)})")
+    taps, ns = kH * 7, (kH * 7 + 1) // 2
+    z = t5.new_zeros(co, 8, kD, 2 * ns)
+    z[:, :ci, :, :taps] = t5.reshape(co, ci, kD, taps)
+    z = z.reshape(co, 8, kD, ns, 2).permute(2, 3, 0, 4, 1).contiguous()       # [kd][s][co][h][ci]
+    return z.half().reshape(-1).view(torch.float32)
+
+
 def conv_precision(n, k, cin, cout, f16=None, train=False):
     """SdcConvDesc.precision for a packed conv weight of n floats (sizes: sdc_pack_conv_weight_floats): the lowest fp32 layout code
     0, 2, 3, 4, 5 whose size matches -- a 1x1x3 buffer packed at 2, 3 or 4 reads as 2, a 3x3 one packed at 3 or 4 as 3 (the same
@@ -193,7 +208,7 @@ class Pool:
 class Plan:
     """Recorded kernel calls; `run(stream)` replays them (the samplers capture that replay into a hipGraph)."""
 
-    def __init__(self, device, precision=0):
+    def __init__(self, device, precision=0, stem_f16=False):
         self.device = torch.device(device)
         self.lib = _lib.get_lib()
         # conv algorithm (include/sdc.h): 0 direct fp32 MFMA | 2 fp32 Winograd F(2,3) along W | 3 F(2x2,3x3) over (H, W) where
@@ -204,6 +219,10 @@ class Plan:
         self.precision = int(precision)
         if self.precision not in (0, 2, 3, 4, 5, 6, 7):
             raise ValueError(f"precision must be 0, 2, 3, 4, 5, 6 or 7 (got {precision})")
+        # net.stem_f16 (opt-in, samplers only, at any precision): the 7-tap stem convs that sdc_conv_stem_f16_ok covers run
+        # conv_stem_f16_kernel (fp16 operands, fp32 accumulation; csrc/sdc_conv_stem_f16.hip) on a buffer of their own
+        # (pack_stem_f16); every other conv, and every conv with the switch off, is recorded exactly as without it
+        self.stem_f16 = bool(stem_f16)
         self.calls = []          # (fn, args, keepalive)
         self.pool = Pool(self.device)
         self.keep = []           # descriptors / tensors that must outlive the plan
@@ -258,15 +277,22 @@ class Plan:
         """Register the kernel layout of a conv weight (pack_conv_weight), refreshed by refresh_weights()."""
         return self.packed(lambda: pack_conv_weight(w() if callable(w) else w, kind, self.precision))
 
+    def stem_weight(self, w):
+        """Register the fp16 buffer of a covered stem conv weight (pack_stem_f16), refreshed by refresh_weights()."""
+        return self.packed(lambda: pack_stem_f16(w() if callable(w) else w))
+
     def vec(self, p):
         return self.packed(lambda: (p() if callable(p) else p).reshape(-1))
 
     # ------------------------------------------------------------------ stages
     def conv(self, x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), up_mode=0,
-             residual=None, out=None, gn_groups=0):
+             residual=None, out=None, gn_groups=0, stem_w=None):
         """x (and optional x1, channel-concatenated) are 5-D views; returns out (B,cout,oD,oH,oW).
         gn_groups > 0: a GroupNorm over `out` follows -- where the conv epilogue can sum its statistics (sdc_conv_gn) the
-        partial sums are kept for the gn_silu call on `out`, which then skips its own pass over the tensor."""
+        partial sums are kept for the gn_silu call on `out`, which then skips its own pass over the tensor.
+        stem_w: the unpacked weight (or a callable returning it) of a conv that may be a 7-tap stem: with Plan.stem_f16, where
+        sdc_conv_stem_f16_ok covers the descriptor, the call recorded is sdc_conv_stem_f16 on its pack_stem_f16 buffer; wp may then
+        be a callable, packed only when the conv takes the usual path."""
         B, c0, iD, iH, iW = x.shape
         c1 = 0 if x1 is None else x1.shape[1]
 
@@ -282,6 +308,17 @@ class Plan:
             # library validates it
             assert tuple(out.shape[:2]) == (B, cout) and out.dim() == 5, (out.shape, (B, cout, *o))
             o = tuple(out.shape[2:])
+        if self.stem_f16 and stem_w is not None and x1 is None and residual is None:
+            d = conv_desc(x, None, out, None, cout, k, stride, pad, up, up_mode, 0)
+            if self.lib.sdc_conv_stem_f16_ok(C.byref(d)):
+                # (gn_groups and split_small_grids are not looked at: the stem kernel neither sums GroupNorm statistics nor splits K;
+                # a gn_silu on `out` finds no partial sums registered and takes its own statistics pass)
+                wh = self.stem_weight(stem_w)
+                self.keep += [d, x, wh, bias, out]
+                self._emit(self.lib.sdc_conv_stem_f16, C.byref(d), _ptr(x), _ptr(wh), _ptr(bias), _ptr(out))
+                return out
+        if callable(wp):
+            wp = wp()
         prec = conv_precision(wp.numel(), k, c0 + c1, cout, f16=self.precision)
         d = conv_desc(x, x1, out, residual, cout, k, stride, pad, up, up_mode, prec)
         if residual is not None:

@@ -226,6 +226,11 @@ class _Builder:
         if pad is None:
             pad = tuple(kk // 2 for kk in k)
         b = self.V(f"{prefix}.bias") if bias else None
+        if self.plan.stem_f16 and kind == "conv" and k[2] == 7:
+            # net.stem_f16: a 7-tap conv; Plan.conv asks the library whether the fp16 stem kernel covers it and packs the
+            # usual buffer only if not
+            return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up, residual=residual,
+                                  out=out, gn_groups=gn_groups, stem_w=lambda: self.net.P(wkey))
         return self.plan.conv(x, self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up,
                               up_mode=1 if kind == "convT" else 0, residual=residual, out=out, gn_groups=gn_groups)
 
@@ -306,6 +311,12 @@ class _HipUNet(nn.Module):
         # strided, upsampling, stem convs, attention, linear layers, norms) stays fp32.  No effect on net(x, t) or the samplers; a
         # live GraphedLossStep keeps the mode it was captured with.  Other values raise ValueError.
         self.train_precision = None
+        # 7-tap stem conv (init_conv) of the sampler plans -- model(x, t), graph-replayed or eager, and the samplers -- on the fp16
+        # matrix pipe (opt-in): fp16 operands rounded to nearest even, fp32 accumulation, where conv_stem_f16_kernel covers it
+        # (Cin <= 8, Cout a multiple of 64, rows of 16 / 32 / 64 / 128: the smoke and Burgers stems at production width; the tokamak
+        # stem, Cin 12, stays fp32).  Works at any `precision`; read when a plan is built, like `precision` (plans are cached per
+        # value).  forward_train, GraphedLossStep and the differentiable DDIM step ignore it.
+        self.stem_f16 = False
         # LinearAttention blocks of width 64 / 128 as the fused 3-launch form (csrc/sdc_lablock.hip); False = the
         # unfused chain norm -> 1x1 -> attention core -> 1x1 -> norm (kept for wider layers and for A/B checks)
         self.fuse_linattn = True
@@ -467,7 +478,7 @@ class _HipUNet(nn.Module):
         """Plan for an input of `shape` whose conditioning table has `rows` rows: one row per sample
         (lut=False, forward(x, time)) or one row per timestep read through a device-side t (lut=True, samplers)."""
         key = (tuple(shape), rows, bool(lut), int(self.precision), bool(self.fuse_linattn), bool(self.subpixel_upsample),
-               bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv))
+               bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16))
         stamp = self._weights_stamp()
         ent = self._plans.get(key)
         if ent is not None and ent["wstamp"] != stamp:        # parameters changed since this plan packed them
@@ -477,7 +488,7 @@ class _HipUNet(nn.Module):
             if dev.type != "cuda":
                 raise RuntimeError("safediffcon_amd runs on MI355X only: move the model to a cuda (HIP) device; "
                                    "there is no CPU fallback")
-            plan = Plan(dev, precision=self.precision)
+            plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16))
             plan.split_small_grids = bool(self.split_small_grids)
             x = torch.zeros(shape, dtype=torch.float32, device=dev)
             eps = torch.zeros(shape, dtype=torch.float32, device=dev)

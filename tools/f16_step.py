@@ -8,9 +8,13 @@
       every conv of the nets' forward plans that the fp16 kernel covers (precision 7: no dispatch table): sdc_conv / sdc_conv_gn
       at precision 4 against 7 on the same buffers, median of 20 launches each -- the data of precision 6's dispatch table
       (csrc/sdc_conv_f16.hip f16_faster)
-  python tools/f16_step.py --drift [T]
+  python tools/f16_step.py --drift [T] [--stem]
       T-step (default 1000) guided smoke trajectories at production width, B = 2, identical Philox noise, precisions 6 and 7
-      against 4
+      against 4; with --stem: precision 4 + net.stem_f16 and 6 + net.stem_f16 against 4 instead
+  python tools/f16_step.py --stem [--workloads c4,c2] [--steps 20] [--warmup 5] [--rounds 2] [--no-step]
+      net.stem_f16 (csrc/sdc_conv_stem_f16.hip): the stem conv of the C4 / C2 plans, today's kernel (sdc_conv at precision 4) against
+      sdc_conv_stem_f16 on the same buffers, median of 20 launches each; then the C4 sampler step, precision 4 against 4 + stem_f16
+      and 6 against 6 + stem_f16, the four arms interleaved round by round
 """
 import _libsel  # noqa: F401  (SDC_LIB_PATH -> safediffcon_amd._lib.use_library, tools only)
 import argparse
@@ -31,22 +35,26 @@ from safediffcon_amd import _lib  # noqa: E402
 DEV = torch.device("cuda:0")
 
 
-def step_ab(names, steps, warmup, rounds, arm=6):
+def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
+    """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16 (default: 4 against `arm`)"""
     torch.cuda.set_device(DEV)
     side = torch.cuda.Stream(device=DEV)
+    arms = list(arms or (4, arm))
     for name in names:
         B = bench.DEFAULT_B[name]
         loops = {}
         with torch.cuda.stream(side), torch.no_grad():
-            for prec in (4, arm):
-                W = bench.workload(name, None, B, DEV, 0, 1, precision=prec, cal_steps=0)
+            for prec in arms:
+                stem = isinstance(prec, str)
+                W = bench.workload(name, None, B, DEV, 0, 1, precision=int(prec.split("+")[0]) if stem else prec, cal_steps=0)
+                W["gd"].model.stem_f16 = stem          # (read when prep() builds the sampler's plan)
                 torch.manual_seed(2)
                 S = W["prep"]()
                 S.init()
                 loops[prec] = S
-            res = {4: [], arm: []}
+            res = {p: [] for p in arms}
             for r in range(rounds):
-                for prec in ((4, arm) if r % 2 == 0 else (arm, 4)):
+                for prec in (arms if r % 2 == 0 else arms[::-1]):
                     S = loops[prec]
 
                     def run(n):
@@ -67,8 +75,9 @@ def step_ab(names, steps, warmup, rounds, arm=6):
                     print(f"[measured] {name} B={B} precision {prec} round {r}: {ms:.2f} ms/step  sclk median "
                           f"{ck.get('sclk_mhz_median')} MHz (min {ck.get('sclk_mhz_min')})  power mean {ck.get('power_w_mean')} W "
                           f"(max {ck.get('power_w_max')})", flush=True)
-            m4, mx = statistics.median(res[4]), statistics.median(res[arm])
-            print(f"[measured] {name}: precision {arm} / 4 = {mx:.2f} / {m4:.2f} ms/step = {mx / m4:.3f}", flush=True)
+            for base, other in zip(arms[0::2], arms[1::2]):
+                m4, mx = statistics.median(res[base]), statistics.median(res[other])
+                print(f"[measured] {name}: precision {other} / {base} = {mx:.2f} / {m4:.2f} ms/step = {mx / m4:.3f}", flush=True)
             for S in loops.values():
                 S.close()
         del loops
@@ -147,21 +156,63 @@ def shapes(names):
         torch.cuda.empty_cache()
 
 
-def drift(T):
+def stem_shapes(names):
+    """the stem conv of the C4 / C2 sampler plans: sdc_conv at precision 4 (today's kernel) against sdc_conv_stem_f16, same buffers"""
+    from safediffcon_amd.engine import as5, conv_desc, pack_conv_weight, pack_stem_f16
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    forms = {   # the state as the net hands it to init_conv, weight shape
+        "c4": (lambda: (torch.randn(64, 32, 7, 64, 64, device=DEV) * 0.5).permute(0, 2, 1, 3, 4), (64, 7, 7, 7, 7)),
+        "c2": (lambda: as5(torch.randn(256, 3, 16, 128, device=DEV) * 0.5), (64, 3, 1, 7, 7)),
+    }
+    name_buf = C.create_string_buffer(96)
+    share = C.c_double(0.0)
+    for wl in names:
+        if wl not in forms:
+            print(f"{wl}: no 7-tap stem that the fp16 kernel covers (c4, c2)", flush=True)
+            continue
+        torch.manual_seed(0)
+        x = forms[wl][0]()
+        co, ci, *k = forms[wl][1]
+        w = torch.randn(co, ci, *k, device=DEV) / (ci * k[0] * k[1] * k[2]) ** 0.5
+        bias = torch.randn(co, device=DEV) * 0.1
+        y4 = torch.empty(x.shape[0], co, *x.shape[2:], device=DEV)
+        yh = torch.empty_like(y4)
+        d = conv_desc(x, None, y4, None, co, tuple(k), (1, 1, 1), tuple(kk // 2 for kk in k), (1, 1, 1), 0, 4)
+        if not lib.sdc_conv_stem_f16_ok(C.byref(d)):
+            print(f"{wl}: stem not covered", flush=True)
+            continue
+        wp, wh = pack_conv_weight(w, precision=4), pack_stem_f16(w)
+        lib.sdc_conv_describe(C.byref(d), name_buf, 96, C.byref(share))
+        ms4 = _time_call(lib.sdc_conv, (C.byref(d), x.data_ptr(), 0, wp.data_ptr(), bias.data_ptr(), 0, y4.data_ptr()), stream)
+        msh = _time_call(lib.sdc_conv_stem_f16, (C.byref(d), x.data_ptr(), wh.data_ptr(), bias.data_ptr(), yh.data_ptr()), stream)
+        npos = d.B * d.oD * d.oH * d.oW
+        flop = 2.0 * npos * co * ci * k[0] * k[1] * k[2]
+        issued = 2.0 * npos * co * k[0] * ((k[1] * 7 + 1) // 2) * 16
+        err = (yh - y4).pow(2).mean().sqrt().item() / y4.pow(2).mean().sqrt().item()
+        print(f"[measured] {wl} stem {k[0]}x{k[1]}x{k[2]} Cin {ci} Cout {co} B {d.B} {d.oD}x{d.oH}x{d.oW}: today {name_buf.value.decode()} "
+              f"{ms4 * 1e3:.1f} us ({flop / ms4 / 1e9:.0f} TFLOP/s) | conv_stem_f16_kernel {msh * 1e3:.1f} us ({flop / msh / 1e9:.0f} TFLOP/s "
+              f"direct-form, {issued / msh / 1e9:.0f} issued) -> x{ms4 / msh:.2f}; rms difference {err:.2e} of the output rms", flush=True)
+        del x, y4, yh
+        torch.cuda.empty_cache()
+
+
+def drift(T, stem=False):
     torch.manual_seed(0)
     net = sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7).to(DEV)
     init = (torch.rand(2, 64, 64) * 0.2).to(DEV)
     control = (torch.randn(2, 32, 2, 64, 64) * 0.3).to(DEV)
     outs = {}
-    for prec in (4, 6, 7):
-        net.precision = prec
+    for prec in ((4, "4+stem", "6+stem") if stem else (4, 6, 7)):
+        net.precision = int(prec.split("+")[0]) if isinstance(prec, str) else prec
+        net.stem_f16 = isinstance(prec, str)
         gs = sdc.GaussianDiffusionSmoke(net, image_size=64, frames=32, timesteps=T, standard_fixed_ratio=100.0).to(DEV)
         torch.manual_seed(7)
         t0 = time.perf_counter()
         outs[prec] = gs.sample(batch_size=2, design_fn=sdc.SmokeGuidance(0.01, 0.9, 0.1), init=init, control=control).cpu()
         print(f"precision {prec}: {time.perf_counter() - t0:.1f} s, finite {bool(torch.isfinite(outs[prec]).all())}, "
               f"|x|max {outs[prec].abs().max():.3f}", flush=True)
-    for p in (6, 7):
+    for p in (("4+stem", "6+stem") if stem else (6, 7)):
         d = (outs[p] - outs[4]).abs()
         print(f"[measured] {T}-step guided smoke trajectories, precision {p} vs 4: max|diff| {d.max():.3e}  mean|diff| {d.mean():.3e}  "
               f"MSE {(d ** 2).mean():.3e}", flush=True)
@@ -176,10 +227,16 @@ if __name__ == "__main__":
     ap.add_argument("--arm", type=int, default=6, choices=(6, 7), help="the precision timed against 4")
     ap.add_argument("--shapes", action="store_true")
     ap.add_argument("--drift", type=int, nargs="?", const=1000, default=None)
+    ap.add_argument("--stem", action="store_true", help="net.stem_f16: the stem launch and the C4 step (with --drift: the stem arms)")
+    ap.add_argument("--no-step", action="store_true", help="--stem: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
-        drift(a.drift)
+        drift(a.drift, a.stem)
+    elif a.stem:
+        stem_shapes([w for w in wls if w != "c3"])
+        if not a.no_step:
+            step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=[4, "4+stem", 6, "6+stem"])
     elif a.shapes:
         shapes(wls)
     else:

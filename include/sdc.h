@@ -415,6 +415,32 @@ size_t sdc_pack_stem_f16_bytes(int Cout, int Cin, int kD, int kH, int kW);
 int sdc_pack_stem_f16(const float* w, void* out, int Cout, int Cin, int kD, int kH, int kW, void* stream);
 int sdc_conv_stem_f16(const SdcConvDesc* d, const float* x, const void* wh, const float* bias, float* y, void* stream);
 
+/* The same stem convs as exact three-way bf16 operand splits on the bf16 matrix pipe (net.stem_split, the nets' default at precision
+ * >= 4, samplers only; csrc/sdc_conv_stem_x3.hip): fp32 inputs, fp32 accumulation, fp32 outputs.  Every fp32
+ * operand is the exact sum of three bf16 pieces, x = h + m + l with h = bf16(x), m = bf16(x - h), l = bf16(x - h - m) (RNE), and a
+ * product is formed as a3 b1 + a2 b2 + a1 b3 + a2 b1 + a1 b2 + a1 b1 (a = weight, b = activation; six v_mfma_f32_32x32x16_bf16, smallest
+ * terms first); the three dropped terms are below 2^-24 |a b|, half an ulp of the product.  An fp32-grade result in another rounding
+ * order, not a reduced precision.  Like stem_f16 a switch of its own beside SdcConvDesc.precision: sdc_conv, its dispatch and every
+ * layout above are untouched; the caller asks sdc_conv_stem_x3_ok and, where it says 1, calls sdc_conv_stem_x3 on the stem's own buffer.
+ *
+ * sdc_conv_stem_x3_ok: 1 where the caller should route the stem here: the predicate of sdc_conv_stem_f16_ok (one function) less the
+ * shapes that did not measure faster than sdc_conv -- the kD = 1 stems (1x1x7 and 1x7x7 taps), so today kD = kH = kW = 7 only.
+ * sdc_conv_stem_x3 itself accepts every descriptor of sdc_conv_stem_f16_ok (SDC_EINVAL for the others).
+ *
+ * Buffer layout (sdc_pack_stem_x3_bytes(...) = 3 * sdc_pack_stem_f16_bytes(...) bytes, 16-byte aligned): three planes
+ *     Wb[piece][kd][s][co][8 h + ci],   piece = 0 (h), 1 (m), 2 (l) of w[co][ci][kd][kh][kw],   kh * 7 + kw = 2 s + h,
+ * each with the layout of Wh above in bf16, zeros where Wh has zeros; the three planes sum to the fp32 weight bit for bit.
+ * sdc_pack_stem_x3 writes it on the device, one launch on `stream`.
+ *
+ * sdc_conv_stem_x3: y = conv(x, w) + bias (bias may be null), asynchronous on `stream`; errors as sdc_conv_stem_f16.  The activations
+ * are split as they are staged.  Fixed k order, no K split, no atomics: deterministic, and a sample's bits do not depend on its batch.
+ * Scaling x by a power of two scales y - bias exactly (short of overflow / underflow).  Non-finite inputs: the residuals of an
+ * infinite x are inf - inf = NaN, so y is NaN where sdc_conv gives an infinity. */
+int sdc_conv_stem_x3_ok(const SdcConvDesc* d);
+size_t sdc_pack_stem_x3_bytes(int Cout, int Cin, int kD, int kH, int kW);
+int sdc_pack_stem_x3(const float* w, void* out, int Cout, int Cin, int kD, int kH, int kW, void* stream);
+int sdc_conv_stem_x3(const SdcConvDesc* d, const float* x, const void* wb, const float* bias, float* y, void* stream);
+
 /* Backward of sdc_gn_apply (GroupNorm -> (scale+1, shift) -> SiLU; Block, conv3d.py:189-204, 1D/model/unet.py:128-147):
  * h = the conv output the forward normalised (contiguous (B,C,S)), stats from the forward, ss = per-sample rows
  * [scale (C) | shift (C)] at ss + b*ss_b_stride or null.  rows: sdc_gn_silu_bwd_floats(B, C, G, S) floats, 8-byte aligned.  Writes

@@ -103,6 +103,13 @@ int launch_f16(const ConvArgs& a, const _Float16* wh, hipStream_t s, const int32
 int pack_f16_tail(const float* w, float* tail, int64_t gap, int Cout, int Cin, int kD, int kH, int kW, hipStream_t s);
 
 // defined in sdc_conv_stem_f16.hip (net.stem_f16)
+// staging geometry of a 64 x 256 stem tile: rows of a plane a tile holds, planes it can touch, slot rows, staged positions; LDS bytes of
+// conv_stem_f16_kernel
+struct StemShape { int Hs, NG, NR, itemsB; size_t lds; };
+StemShape stem_shape(const SdcConvDesc& d);
 int launch_stem_f16(const SdcConvDesc& d, const float* x, const _Float16* wh, const float* bias, float* y, hipStream_t s);
+
+// defined in sdc_conv_stem_x3.hip (net.stem_split)
+int launch_stem_x3(const SdcConvDesc& d, const float* x, const __bf16* wb, const float* bias, float* y, hipStream_t s);
 
 }  // namespace sdcconv

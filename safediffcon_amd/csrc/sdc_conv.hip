@@ -1964,6 +1964,21 @@ extern "C" int sdc_conv_stem_f16(const SdcConvDesc* dp, const float* x, const vo
     return launch_stem_f16(*dp, x, reinterpret_cast<const _Float16*>(wh), bias, y, sdc::as_stream(stream));
 }
 
+// net.stem_split (include/sdc.h): the same stems as exact three-way bf16 operand splits on the bf16 matrix pipe (sdc_conv_stem_x3.hip).
+// Coverage starts as that of the fp16 stem kernel -- one predicate, descriptor only, never keyed on B -- less what did not measure
+// faster than conv_rh_kernel: the kD = 1 stems (the C2 stem, 1x7x7: 149 against 149 us, inside the spread of the repeated medians;
+// DESIGN.md section 14).  The kernel itself runs every descriptor of stem_f16_ok, and sdc_conv_stem_x3 accepts them (tests, measurement).
+extern "C" int sdc_conv_stem_x3_ok(const SdcConvDesc* dp) {
+    return dp && stem_f16_ok(*dp) && dp->kD == 7 ? 1 : 0;
+}
+
+extern "C" int sdc_conv_stem_x3(const SdcConvDesc* dp, const float* x, const void* wb, const float* bias, float* y, void* stream) {
+    SDC_REQUIRE(dp && x && wb && y, SDC_ENULL, "sdc_conv_stem_x3: null pointer");
+    SDC_REQUIRE(stem_f16_ok(*dp), SDC_EINVAL, "sdc_conv_stem_x3: descriptor not covered (sdc_conv_stem_f16_ok returned 0): %dx%dx%d taps, Cin %d+%d, "
+                "Cout %d, rows of %d", dp->kD, dp->kH, dp->kW, dp->Cin0, dp->Cin1, dp->Cout, dp->oW);
+    return launch_stem_x3(*dp, x, reinterpret_cast<const __bf16*>(wb), bias, y, sdc::as_stream(stream));
+}
+
 namespace {
 
 int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const float* wp, const float* bias,

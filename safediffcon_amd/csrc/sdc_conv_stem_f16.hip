@@ -222,25 +222,6 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ?
     }
 }
 
-struct StemShape { int Hs, NG, NR, itemsB; size_t lds; };
-
-StemShape stem_shape(const SdcConvDesc& d) {
-    StemShape sh{};
-    const int W = d.oW, R = SF_BN / W, NS = (d.kH * 7 + 1) / 2;
-    if (d.kH == 1) { sh.Hs = R; sh.NG = 1; }
-    else {
-        sh.Hs = d.oH < R ? d.oH : R;
-        // tiles start at multiples of R rows: aligned with the planes when oH divides R or R divides oH; else a tile's R rows
-        // touch at most (R - 1) / oH + 2 planes
-        const bool al = d.oH % R == 0 || R % d.oH == 0;
-        sh.NG = al ? (d.oH >= R ? 1 : R / d.oH) : (R - 1) / d.oH + 2;
-    }
-    sh.NR = sh.NG * (sh.Hs + d.kH - 1);
-    sh.itemsB = sh.NR * W;
-    sh.lds = (size_t)NS * SF_BM * 32 + (size_t)sh.NR * (W + 6) * 16;
-    return sh;
-}
-
 // Wh[kd][s][co][8 h + ci] = (fp16, RNE) w[co][ci][kd][tap = 2 s + h], zero for tap >= 7 kH and for ci >= Cin; one thread per half
 __global__ __launch_bounds__(256) void pack_stem_f16_kernel(const float* __restrict__ w, _Float16* __restrict__ out, int Cout, int Cin, int kD,
                                                             int taps, int NS, int64_t n) {
@@ -262,6 +243,23 @@ bool stem_taps_ok(int Cin, int kD, int kH, int kW) {
 }  // namespace
 
 namespace sdcconv {
+
+StemShape stem_shape(const SdcConvDesc& d) {
+    StemShape sh{};
+    const int W = d.oW, R = SF_BN / W, NS = (d.kH * 7 + 1) / 2;
+    if (d.kH == 1) { sh.Hs = R; sh.NG = 1; }
+    else {
+        sh.Hs = d.oH < R ? d.oH : R;
+        // tiles start at multiples of R rows: aligned with the planes when oH divides R or R divides oH; else a tile's R rows
+        // touch at most (R - 1) / oH + 2 planes
+        const bool al = d.oH % R == 0 || R % d.oH == 0;
+        sh.NG = al ? (d.oH >= R ? 1 : R / d.oH) : (R - 1) / d.oH + 2;
+    }
+    sh.NR = sh.NG * (sh.Hs + d.kH - 1);
+    sh.itemsB = sh.NR * W;
+    sh.lds = (size_t)NS * SF_BM * 32 + (size_t)sh.NR * (W + 6) * 16;
+    return sh;
+}
 
 int launch_stem_f16(const SdcConvDesc& d, const float* x, const _Float16* wh, const float* bias, float* y, hipStream_t s) {
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wh) % 16 == 0, SDC_EALIGN, "sdc_conv_stem_f16: the packed weight buffer must be 16-byte aligned");

@@ -148,6 +148,30 @@ def pack_stem_f16(w):
     return z.half().reshape(-1).view(torch.float32)
 
 
+def pack_stem_x3(w):
+    """bf16 buffer of a 7-tap stem conv weight for sdc_conv_stem_x3 (include/sdc.h; host twin of sdc_pack_stem_x3, bit for bit): three
+    planes Wb[piece][kd][s][co][8 h + ci], each with the layout of pack_stem_f16, holding the exact three-way split of the fp32 weight
+    -- h = bf16(w), m = bf16(w - h), l = bf16(w - h - m), all RNE, h + m + l == w -- zero for ci >= Cin and for the one tap past the
+    end; returned as the float32 words that hold it"""
+    t5 = as5(w).to(torch.float32)
+    co, ci, kD, kH, kW = t5.shape
+    if not (kW == 7 and (kD, kH) in ((1, 1), (1, 7), (7, 7)) and 1 <= ci <= 8):
+        raise ValueError(f"pack_stem_x3: taps 1x1x7, 1x7x7 or 7x7x7 and Cin <= 8 (got {tuple(t5.shape)})")
+    taps, ns = kH * 7, (kH * 7 + 1) // 2
+    z = t5.new_zeros(co, 8, kD, 2 * ns)
+    z[:, :ci, :, :taps] = t5.reshape(co, ci, kD, taps)
+    z = z.reshape(co, 8, kD, ns, 2).permute(2, 3, 0, 4, 1).contiguous()       # [kd][s][co][h][ci]
+    return torch.stack(split3_bf16(z)).reshape(-1).view(torch.float32)
+
+
+def split3_bf16(x):
+    """the exact three-way bf16 split of a finite fp32 tensor: (h, m, l) bfloat16 with h + m + l == x (RNE conversions, exact residuals)"""
+    h = x.bfloat16()
+    r = x - h.float()
+    m = r.bfloat16()
+    return h, m, (r - m.float()).bfloat16()
+
+
 def conv_precision(n, k, cin, cout, f16=None, train=False):
     """SdcConvDesc.precision for a packed conv weight of n floats (sizes: sdc_pack_conv_weight_floats): the lowest fp32 layout code
     0, 2, 3, 4, 5 whose size matches -- a 1x1x3 buffer packed at 2, 3 or 4 reads as 2, a 3x3 one packed at 3 or 4 as 3 (the same
@@ -208,7 +232,7 @@ class Pool:
 class Plan:
     """Recorded kernel calls; `run(stream)` replays them (the samplers capture that replay into a hipGraph)."""
 
-    def __init__(self, device, precision=0, stem_f16=False):
+    def __init__(self, device, precision=0, stem_f16=False, stem_split=False):
         self.device = torch.device(device)
         self.lib = _lib.get_lib()
         # conv algorithm (include/sdc.h): 0 direct fp32 MFMA | 2 fp32 Winograd F(2,3) along W | 3 F(2x2,3x3) over (H, W) where
@@ -223,6 +247,10 @@ class Plan:
         # conv_stem_f16_kernel (fp16 operands, fp32 accumulation; csrc/sdc_conv_stem_f16.hip) on a buffer of their own
         # (pack_stem_f16); every other conv, and every conv with the switch off, is recorded exactly as without it
         self.stem_f16 = bool(stem_f16)
+        # net.stem_split (the nets' default at precision >= 4, samplers only; off for a Plan built directly): the same stems run
+        # conv_stem_x3_kernel -- fp32 products formed on the bf16 matrix pipe from exact three-way operand splits, fp32 accumulation
+        # (csrc/sdc_conv_stem_x3.hip) -- on their pack_stem_x3 buffer.  Precision 0, 2 and 3 keep the literal fp32 pipe; stem_f16 wins
+        self.stem_split = bool(stem_split) and self.precision >= 4 and not self.stem_f16
         self.calls = []          # (fn, args, keepalive)
         self.pool = Pool(self.device)
         self.keep = []           # descriptors / tensors that must outlive the plan
@@ -277,9 +305,9 @@ class Plan:
         """Register the kernel layout of a conv weight (pack_conv_weight), refreshed by refresh_weights()."""
         return self.packed(lambda: pack_conv_weight(w() if callable(w) else w, kind, self.precision))
 
-    def stem_weight(self, w):
-        """Register the fp16 buffer of a covered stem conv weight (pack_stem_f16), refreshed by refresh_weights()."""
-        return self.packed(lambda: pack_stem_f16(w() if callable(w) else w))
+    def stem_weight(self, w, pack=pack_stem_f16):
+        """Register the 16-bit buffer of a covered stem conv weight (pack_stem_f16 / pack_stem_x3), refreshed by refresh_weights()."""
+        return self.packed(lambda: pack(w() if callable(w) else w))
 
     def vec(self, p):
         return self.packed(lambda: (p() if callable(p) else p).reshape(-1))
@@ -291,8 +319,9 @@ class Plan:
         gn_groups > 0: a GroupNorm over `out` follows -- where the conv epilogue can sum its statistics (sdc_conv_gn) the
         partial sums are kept for the gn_silu call on `out`, which then skips its own pass over the tensor.
         stem_w: the unpacked weight (or a callable returning it) of a conv that may be a 7-tap stem: with Plan.stem_f16, where
-        sdc_conv_stem_f16_ok covers the descriptor, the call recorded is sdc_conv_stem_f16 on its pack_stem_f16 buffer; wp may then
-        be a callable, packed only when the conv takes the usual path."""
+        sdc_conv_stem_f16_ok covers the descriptor, the call recorded is sdc_conv_stem_f16 on its pack_stem_f16 buffer; with
+        Plan.stem_split, where sdc_conv_stem_x3_ok does, sdc_conv_stem_x3 on its pack_stem_x3 buffer; wp may then be a callable,
+        packed only when the conv takes the usual path."""
         B, c0, iD, iH, iW = x.shape
         c1 = 0 if x1 is None else x1.shape[1]
 
@@ -308,14 +337,16 @@ class Plan:
             # library validates it
             assert tuple(out.shape[:2]) == (B, cout) and out.dim() == 5, (out.shape, (B, cout, *o))
             o = tuple(out.shape[2:])
-        if self.stem_f16 and stem_w is not None and x1 is None and residual is None:
+        if (self.stem_f16 or self.stem_split) and stem_w is not None and x1 is None and residual is None:
             d = conv_desc(x, None, out, None, cout, k, stride, pad, up, up_mode, 0)
-            if self.lib.sdc_conv_stem_f16_ok(C.byref(d)):
-                # (gn_groups and split_small_grids are not looked at: the stem kernel neither sums GroupNorm statistics nor splits K;
+            ok, fn, pack = ((self.lib.sdc_conv_stem_f16_ok, self.lib.sdc_conv_stem_f16, pack_stem_f16) if self.stem_f16 else
+                            (self.lib.sdc_conv_stem_x3_ok, self.lib.sdc_conv_stem_x3, pack_stem_x3))
+            if ok(C.byref(d)):
+                # (gn_groups and split_small_grids are not looked at: the stem kernels neither sum GroupNorm statistics nor split K;
                 # a gn_silu on `out` finds no partial sums registered and takes its own statistics pass)
-                wh = self.stem_weight(stem_w)
+                wh = self.stem_weight(stem_w, pack)
                 self.keep += [d, x, wh, bias, out]
-                self._emit(self.lib.sdc_conv_stem_f16, C.byref(d), _ptr(x), _ptr(wh), _ptr(bias), _ptr(out))
+                self._emit(fn, C.byref(d), _ptr(x), _ptr(wh), _ptr(bias), _ptr(out))
                 return out
         if callable(wp):
             wp = wp()

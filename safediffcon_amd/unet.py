@@ -226,8 +226,8 @@ class _Builder:
         if pad is None:
             pad = tuple(kk // 2 for kk in k)
         b = self.V(f"{prefix}.bias") if bias else None
-        if self.plan.stem_f16 and kind == "conv" and k[2] == 7:
-            # net.stem_f16: a 7-tap conv; Plan.conv asks the library whether the fp16 stem kernel covers it and packs the
+        if (self.plan.stem_f16 or self.plan.stem_split) and kind == "conv" and k[2] == 7:
+            # net.stem_f16 / net.stem_split: a 7-tap conv; Plan.conv asks the library whether the stem kernel covers it and packs the
             # usual buffer only if not
             return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up, residual=residual,
                                   out=out, gn_groups=gn_groups, stem_w=lambda: self.net.P(wkey))
@@ -317,6 +317,13 @@ class _HipUNet(nn.Module):
         # stem, Cin 12, stays fp32).  Works at any `precision`; read when a plan is built, like `precision` (plans are cached per
         # value).  forward_train, GraphedLossStep and the differentiable DDIM step ignore it.
         self.stem_f16 = False
+        # the same stem conv of the sampler plans at precision >= 4 (default on): fp32 products formed on the bf16 matrix pipe from
+        # exact three-way operand splits (x = bf16 h + m + l, six MFMAs per product, fp32 accumulation; conv_stem_x3_kernel) where it
+        # covers the stem (the coverage of stem_f16).  An fp32-grade result in another rounding order, like the Winograd modes -- not a
+        # reduced precision: at precision 0, 2 and 3 the stem stays on the literal fp32 pipe whatever this says, stem_f16 wins when
+        # both are set, and forward_train, GraphedLossStep and the differentiable DDIM step never see it.  False = conv_rh_kernel
+        # (A/B checks).  Read when a plan is built (plans are cached per value).
+        self.stem_split = True
         # LinearAttention blocks of width 64 / 128 as the fused 3-launch form (csrc/sdc_lablock.hip); False = the
         # unfused chain norm -> 1x1 -> attention core -> 1x1 -> norm (kept for wider layers and for A/B checks)
         self.fuse_linattn = True
@@ -478,7 +485,8 @@ class _HipUNet(nn.Module):
         """Plan for an input of `shape` whose conditioning table has `rows` rows: one row per sample
         (lut=False, forward(x, time)) or one row per timestep read through a device-side t (lut=True, samplers)."""
         key = (tuple(shape), rows, bool(lut), int(self.precision), bool(self.fuse_linattn), bool(self.subpixel_upsample),
-               bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16))
+               bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16),
+               bool(self.stem_split))
         stamp = self._weights_stamp()
         ent = self._plans.get(key)
         if ent is not None and ent["wstamp"] != stamp:        # parameters changed since this plan packed them
@@ -488,7 +496,7 @@ class _HipUNet(nn.Module):
             if dev.type != "cuda":
                 raise RuntimeError("safediffcon_amd runs on MI355X only: move the model to a cuda (HIP) device; "
                                    "there is no CPU fallback")
-            plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16))
+            plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16), stem_split=bool(self.stem_split))
             plan.split_small_grids = bool(self.split_small_grids)
             x = torch.zeros(shape, dtype=torch.float32, device=dev)
             eps = torch.zeros(shape, dtype=torch.float32, device=dev)

@@ -15,6 +15,9 @@
       net.stem_f16 (csrc/sdc_conv_stem_f16.hip): the stem conv of the C4 / C2 plans, today's kernel (sdc_conv at precision 4) against
       sdc_conv_stem_f16 on the same buffers, median of 20 launches each; then the C4 sampler step, precision 4 against 4 + stem_f16
       and 6 against 6 + stem_f16, the four arms interleaved round by round
+  python tools/f16_step.py --split [--workloads c4,c2] [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
+      net.stem_split (csrc/sdc_conv_stem_x3.hip, default on): the same stem launches, today's fp32 kernel against sdc_conv_stem_x3 (the
+      medians of three interleaved repeats, so that their spread shows); then the C4 sampler step with the switch off against on
 """
 import _libsel  # noqa: F401  (SDC_LIB_PATH -> safediffcon_amd._lib.use_library, tools only)
 import argparse
@@ -36,7 +39,8 @@ DEV = torch.device("cuda:0")
 
 
 def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
-    """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16 (default: 4 against `arm`)"""
+    """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16, 'P-nosplit' precision P with
+    net.stem_split off (default: 4 against `arm`)"""
     torch.cuda.set_device(DEV)
     side = torch.cuda.Stream(device=DEV)
     arms = list(arms or (4, arm))
@@ -45,9 +49,10 @@ def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
         loops = {}
         with torch.cuda.stream(side), torch.no_grad():
             for prec in arms:
-                stem = isinstance(prec, str)
-                W = bench.workload(name, None, B, DEV, 0, 1, precision=int(prec.split("+")[0]) if stem else prec, cal_steps=0)
-                W["gd"].model.stem_f16 = stem          # (read when prep() builds the sampler's plan)
+                tag = str(prec)
+                W = bench.workload(name, None, B, DEV, 0, 1, precision=int(tag.split("+")[0].split("-")[0]), cal_steps=0)
+                W["gd"].model.stem_f16 = tag.endswith("+stem")          # (read when prep() builds the sampler's plan)
+                W["gd"].model.stem_split = not tag.endswith("-nosplit")
                 torch.manual_seed(2)
                 S = W["prep"]()
                 S.init()
@@ -156,9 +161,10 @@ def shapes(names):
         torch.cuda.empty_cache()
 
 
-def stem_shapes(names):
-    """the stem conv of the C4 / C2 sampler plans: sdc_conv at precision 4 (today's kernel) against sdc_conv_stem_f16, same buffers"""
-    from safediffcon_amd.engine import as5, conv_desc, pack_conv_weight, pack_stem_f16
+def stem_shapes(names, split=False):
+    """the stem conv of the C4 / C2 sampler plans: sdc_conv at precision 4 (today's kernel) against sdc_conv_stem_f16 -- split: against
+    sdc_conv_stem_x3 --, same buffers"""
+    from safediffcon_amd.engine import as5, conv_desc, pack_conv_weight, pack_stem_f16, pack_stem_x3
     lib = _lib.get_lib()
     stream = torch.cuda.current_stream().cuda_stream
     forms = {   # the state as the net hands it to init_conv, weight shape
@@ -184,10 +190,27 @@ def stem_shapes(names):
             continue
         wp, wh = pack_conv_weight(w, precision=4), pack_stem_f16(w)
         lib.sdc_conv_describe(C.byref(d), name_buf, 96, C.byref(share))
-        ms4 = _time_call(lib.sdc_conv, (C.byref(d), x.data_ptr(), 0, wp.data_ptr(), bias.data_ptr(), 0, y4.data_ptr()), stream)
-        msh = _time_call(lib.sdc_conv_stem_f16, (C.byref(d), x.data_ptr(), wh.data_ptr(), bias.data_ptr(), yh.data_ptr()), stream)
         npos = d.B * d.oD * d.oH * d.oW
         flop = 2.0 * npos * co * ci * k[0] * k[1] * k[2]
+        if split:
+            wb = pack_stem_x3(w)
+            m4, mx = [], []
+            for _ in range(3):      # interleaved repeats of the median of 20: their spread is what a gain has to beat
+                m4.append(_time_call(lib.sdc_conv, (C.byref(d), x.data_ptr(), 0, wp.data_ptr(), bias.data_ptr(), 0, y4.data_ptr()), stream))
+                mx.append(_time_call(lib.sdc_conv_stem_x3, (C.byref(d), x.data_ptr(), wb.data_ptr(), bias.data_ptr(), yh.data_ptr()), stream))
+            ref = torch.nn.functional.conv3d(x[:1].double(), w.double(), bias.double(), padding=tuple(kk // 2 for kk in k))
+            rms = ref.pow(2).mean().sqrt().item()
+            e4, ex = ((y[:1].double() - ref).pow(2).mean().sqrt().item() / rms for y in (y4, yh))
+            a4, ax = statistics.median(m4), statistics.median(mx)
+            print(f"[measured] {wl} stem {k[0]}x{k[1]}x{k[2]} Cin {ci} Cout {co} B {d.B} {d.oD}x{d.oH}x{d.oW}: today {name_buf.value.decode()} "
+                  f"{' / '.join(f'{v * 1e3:.1f}' for v in m4)} us ({flop / a4 / 1e9:.0f} TFLOP/s) | conv_stem_x3_kernel "
+                  f"{' / '.join(f'{v * 1e3:.1f}' for v in mx)} us ({flop / ax / 1e9:.0f} TFLOP/s direct-form) -> x{a4 / ax:.2f}; rms error "
+                  f"against fp64 on sample 0, of the output rms: today {e4:.2e}, split {ex:.2e}", flush=True)
+            del x, y4, yh, ref
+            torch.cuda.empty_cache()
+            continue
+        ms4 = _time_call(lib.sdc_conv, (C.byref(d), x.data_ptr(), 0, wp.data_ptr(), bias.data_ptr(), 0, y4.data_ptr()), stream)
+        msh = _time_call(lib.sdc_conv_stem_f16, (C.byref(d), x.data_ptr(), wh.data_ptr(), bias.data_ptr(), yh.data_ptr()), stream)
         issued = 2.0 * npos * co * k[0] * ((k[1] * 7 + 1) // 2) * 16
         err = (yh - y4).pow(2).mean().sqrt().item() / y4.pow(2).mean().sqrt().item()
         print(f"[measured] {wl} stem {k[0]}x{k[1]}x{k[2]} Cin {ci} Cout {co} B {d.B} {d.oD}x{d.oH}x{d.oW}: today {name_buf.value.decode()} "
@@ -228,11 +251,16 @@ if __name__ == "__main__":
     ap.add_argument("--shapes", action="store_true")
     ap.add_argument("--drift", type=int, nargs="?", const=1000, default=None)
     ap.add_argument("--stem", action="store_true", help="net.stem_f16: the stem launch and the C4 step (with --drift: the stem arms)")
-    ap.add_argument("--no-step", action="store_true", help="--stem: the per-shape part only")
+    ap.add_argument("--split", action="store_true", help="net.stem_split: the stem launch and the C4 step with the switch off / on")
+    ap.add_argument("--no-step", action="store_true", help="--stem / --split: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
         drift(a.drift, a.stem)
+    elif a.split:
+        stem_shapes([w for w in wls if w != "c3"], split=True)
+        if not a.no_step:
+            step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=["4-nosplit", 4])
     elif a.stem:
         stem_shapes([w for w in wls if w != "c3"])
         if not a.no_step:

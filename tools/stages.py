@@ -43,6 +43,14 @@ def classify(lib, fn, a):
             kern += " splitk"
         fl = 2.0 * P * d.Cout * cin * taps
         return dict(stage=kind, kernel=kern, flops=fl, issued=fl * share, bytes=by)
+    if fn is lib.sdc_conv_stem_x3:
+        # (d, x, wb, bias, y): the direct-form FLOP of the conv it stands for; its six bf16 MFMAs per product run on another pipe, so
+        # nothing is booked as fp32-MFMA issue (the column rated against the fp32 peak stays 0)
+        d = a[0]._obj
+        P, taps = d.B * d.oD * d.oH * d.oW, d.kD * d.kH * d.kW
+        return dict(stage=f"conv {d.kD}x{d.kH}x{d.kW} [stem, bf16 split: exact 3-way operand splits on the bf16 matrix pipe]",
+                    kernel="conv_stem_x3_kernel", flops=2.0 * P * d.Cout * d.Cin0 * taps, issued=0.0,
+                    bytes=4.0 * (d.B * d.Cin0 * d.iD * d.iH * d.iW + P * d.Cout + taps * d.Cin0 * d.Cout))
     if fn is lib.sdc_gn_finalize:
         return dict(stage="groupnorm stats (finalize of the conv-epilogue sums)", kernel="gn_finalize", flops=0.0, issued=0.0, bytes=0.0)
     if fn is lib.sdc_gn_stats:

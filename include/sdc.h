@@ -441,6 +441,40 @@ size_t sdc_pack_stem_x3_bytes(int Cout, int Cin, int kD, int kH, int kW);
 int sdc_pack_stem_x3(const float* w, void* out, int Cout, int Cin, int kD, int kH, int kW, void* stream);
 int sdc_conv_stem_x3(const SdcConvDesc* d, const float* x, const void* wb, const float* bias, float* y, void* stream);
 
+/* The strided (1,4,4)/(1,2,2) convs, the 1x2x2 sub-pixel convs of the transposed convs and the 1x1x1 convs as exact three-way bf16 operand
+ * splits on the bf16 matrix pipe (net.gemm_split, default on at precision >= 4, samplers only; DESIGN.md section 15;
+ * csrc/sdc_conv_gemm_x3.hip): the arithmetic of sdc_conv_stem_x3 -- fp32 inputs, fp32 accumulation, fp32 outputs, six
+ * v_mfma_f32_32x32x16_bf16 per product, fixed k order, no K split, no atomics.  A switch of its own beside SdcConvDesc.precision:
+ * sdc_conv, its dispatch and every layout above are untouched; the caller asks sdc_conv_gemm_x3_ok and, where it says 1, calls
+ * sdc_conv_gemm_x3 on the conv's own buffer.
+ *
+ * Covered: kD = 1, one input tensor (Cin1 == 0), no residual (rs all zero), no upsampling, Cout % 64 == 0, rows of 16 / 32 / 64 / 128
+ * output columns, and one of
+ *   taps (1,4,4), stride (1,2,2), pad (0,1,1), input twice the output along H and W, Cin % 16 == 0;
+ *   taps (1,2,2), stride 1, pad (0, pH, pW) with pH, pW in {0, 1}, output size = input size, Cin % 32 == 0 (y is usually a parity view
+ *     y[:, :, :, 1 - pH :: 2, 1 - pW :: 2] of a transposed conv's output: every stride of y is free);
+ *   taps 1x1x1, stride 1, Cin % 64 == 0;
+ * with a tile's input rows within 160 KB of LDS.  There is no form with a second input, a residual, GroupNorm sums or upsampling.
+ *
+ * sdc_conv_gemm_x3_ok: 1 where the caller should route the conv here: covered AND measured faster than sdc_conv at precision 4 on the
+ * same buffers (the table in csrc/sdc_conv_gemm_x3.hip).  Host only, launches nothing, reads the descriptor only, keyed on per-sample
+ * sizes and never on B: a sample's bits do not depend on its batch.  sdc_conv_gemm_x3 itself accepts every covered descriptor
+ * (tests, measurement) and returns SDC_EINVAL for the others.
+ *
+ * Buffer layout (sdc_pack_gemm_x3_bytes(Cout, Cin, kH, kW) = 3 * kH * kW * Cin * Cout * 2 bytes, 16-byte aligned; 0 for other taps or
+ * channel counts): three bf16 planes, the exact split h = bf16(w), m = bf16(w - h), l = bf16(w - h - m) (RNE), each
+ * Wb[m tile = co / 64][stage][step = block * taps + tap][co % 64][ci % 16] with ci = (stage * NCB + block) * 16 + ci % 16 and
+ * NCB = 1 (4x4 taps), 2 (2x2) or 4 (1x1) channel blocks of 16 per stage: the steps of a stage are one contiguous run per tile.
+ * sdc_pack_gemm_x3 writes it on the device, one launch on `stream`, from the conv's Wp[tap * Cin + ci][co] (the precision-0 layout of
+ * sdc_conv; for a sub-pixel conv the merged sub-filter of its parity).
+ *
+ * sdc_conv_gemm_x3: y = conv(x, w) + bias (bias may be null), asynchronous on `stream`.  SDC_ENULL for a null d, x, wb or y,
+ * SDC_EINVAL for a descriptor that is not covered, both before any launch; SDC_EALIGN for a misaligned wb. */
+int sdc_conv_gemm_x3_ok(const SdcConvDesc* d);
+size_t sdc_pack_gemm_x3_bytes(int Cout, int Cin, int kH, int kW);
+int sdc_pack_gemm_x3(const float* wp, void* out, int Cout, int Cin, int kH, int kW, void* stream);
+int sdc_conv_gemm_x3(const SdcConvDesc* d, const float* x, const void* wb, const float* bias, float* y, void* stream);
+
 /* Backward of sdc_gn_apply (GroupNorm -> (scale+1, shift) -> SiLU; Block, conv3d.py:189-204, 1D/model/unet.py:128-147):
  * h = the conv output the forward normalised (contiguous (B,C,S)), stats from the forward, ss = per-sample rows
  * [scale (C) | shift (C)] at ss + b*ss_b_stride or null.  rows: sdc_gn_silu_bwd_floats(B, C, G, S) floats, 8-byte aligned.  Writes

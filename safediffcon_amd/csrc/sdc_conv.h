@@ -112,4 +112,8 @@ int launch_stem_f16(const SdcConvDesc& d, const float* x, const _Float16* wh, co
 // defined in sdc_conv_stem_x3.hip (net.stem_split)
 int launch_stem_x3(const SdcConvDesc& d, const float* x, const __bf16* wb, const float* bias, float* y, hipStream_t s);
 
+// defined in sdc_conv_gemm_x3.hip (net.gemm_split)
+bool gemm_x3_covers(const SdcConvDesc& d);     // conv_gemm_x3_kernel runs this descriptor (sdc_conv_gemm_x3_ok: and measured faster)
+int launch_gemm_x3(const SdcConvDesc& d, const float* x, const __bf16* wb, const float* bias, float* y, hipStream_t s);
+
 }  // namespace sdcconv

@@ -164,6 +164,23 @@ def pack_stem_x3(w):
     return torch.stack(split3_bf16(z)).reshape(-1).view(torch.float32)
 
 
+def pack_gemm_x3(wp, cout, cin, k):
+    """bf16 buffer of a strided (1,4,4), sub-pixel (1,2,2) or 1x1x1 conv weight for sdc_conv_gemm_x3 (include/sdc.h; host twin of
+    sdc_pack_gemm_x3, bit for bit) from the conv's Wp [taps * Cin][Cout] (pack_conv_weight at precision 0; for a sub-pixel conv the merged
+    sub-filter of its parity): three planes Wb[piece][co // 64][stage][block * taps + tap][co % 64][ci % 16], ci = (stage * NCB + block) *
+    16 + ci % 16 with NCB = 1 / 2 / 4 channel blocks per stage for 4x4 / 2x2 / 1x1 taps, holding the exact three-way split of the fp32
+    weight (h + m + l == w); returned as the float32 words that hold it"""
+    k = tuple(k)[-2:]
+    ncb = {(4, 4): 1, (2, 2): 2, (1, 1): 4}.get(k, 0)
+    taps = k[0] * k[1]
+    if ncb == 0 or cout <= 0 or cout % 64 or cin <= 0 or cin % (16 * ncb) or tuple(wp.shape) != (taps * cin, cout):
+        raise ValueError(f"pack_gemm_x3: taps 4x4, 2x2 or 1x1, Cout % 64 == 0, Cin % {16 * max(ncb, 1)} == 0, Wp [taps * Cin][Cout] "
+                         f"(got taps {k}, Cin {cin}, Cout {cout}, Wp {tuple(wp.shape)})")
+    z = wp.to(torch.float32).reshape(taps, cin // (16 * ncb), ncb, 16, cout // 64, 64)      # [tap][stage][block][c16][m tile][co]
+    z = z.permute(4, 1, 2, 0, 5, 3).contiguous()                                             # [m tile][stage][block][tap][co][c16]
+    return torch.stack(split3_bf16(z)).reshape(-1).view(torch.float32)
+
+
 def split3_bf16(x):
     """the exact three-way bf16 split of a finite fp32 tensor: (h, m, l) bfloat16 with h + m + l == x (RNE conversions, exact residuals)"""
     h = x.bfloat16()
@@ -232,7 +249,7 @@ class Pool:
 class Plan:
     """Recorded kernel calls; `run(stream)` replays them (the samplers capture that replay into a hipGraph)."""
 
-    def __init__(self, device, precision=0, stem_f16=False, stem_split=False):
+    def __init__(self, device, precision=0, stem_f16=False, stem_split=False, gemm_split=False):
         self.device = torch.device(device)
         self.lib = _lib.get_lib()
         # conv algorithm (include/sdc.h): 0 direct fp32 MFMA | 2 fp32 Winograd F(2,3) along W | 3 F(2x2,3x3) over (H, W) where
@@ -251,6 +268,11 @@ class Plan:
         # conv_stem_x3_kernel -- fp32 products formed on the bf16 matrix pipe from exact three-way operand splits, fp32 accumulation
         # (csrc/sdc_conv_stem_x3.hip) -- on their pack_stem_x3 buffer.  Precision 0, 2 and 3 keep the literal fp32 pipe; stem_f16 wins
         self.stem_split = bool(stem_split) and self.precision >= 4 and not self.stem_f16
+        # net.gemm_split (the nets' default at precision >= 4, samplers only; off for a Plan built directly): the strided (1,4,4), the
+        # sub-pixel (1,2,2) convs of conv_transpose_422 and the 1x1x1 convs that sdc_conv_gemm_x3_ok lists -- covered by
+        # conv_gemm_x3_kernel (csrc/sdc_conv_gemm_x3.hip: the stem_split arithmetic) and measured faster than the fp32 kernel -- run it on
+        # their pack_gemm_x3 buffer.  Precision 0, 2 and 3 keep the literal fp32 pipe
+        self.gemm_split = bool(gemm_split) and self.precision >= 4
         self.calls = []          # (fn, args, keepalive)
         self.pool = Pool(self.device)
         self.keep = []           # descriptors / tensors that must outlive the plan
@@ -314,14 +336,16 @@ class Plan:
 
     # ------------------------------------------------------------------ stages
     def conv(self, x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), up_mode=0,
-             residual=None, out=None, gn_groups=0, stem_w=None):
+             residual=None, out=None, gn_groups=0, stem_w=None, gemm_w=None):
         """x (and optional x1, channel-concatenated) are 5-D views; returns out (B,cout,oD,oH,oW).
         gn_groups > 0: a GroupNorm over `out` follows -- where the conv epilogue can sum its statistics (sdc_conv_gn) the
         partial sums are kept for the gn_silu call on `out`, which then skips its own pass over the tensor.
         stem_w: the unpacked weight (or a callable returning it) of a conv that may be a 7-tap stem: with Plan.stem_f16, where
         sdc_conv_stem_f16_ok covers the descriptor, the call recorded is sdc_conv_stem_f16 on its pack_stem_f16 buffer; with
         Plan.stem_split, where sdc_conv_stem_x3_ok does, sdc_conv_stem_x3 on its pack_stem_x3 buffer; wp may then be a callable,
-        packed only when the conv takes the usual path."""
+        packed only when the conv takes the usual path.
+        gemm_w: a callable returning the conv's Wp [taps * Cin][Cout] (pack_conv_weight at precision 0): with Plan.gemm_split, where
+        sdc_conv_gemm_x3_ok lists the descriptor, the call recorded is sdc_conv_gemm_x3 on its pack_gemm_x3 buffer (wp as for stem_w)."""
         B, c0, iD, iH, iW = x.shape
         c1 = 0 if x1 is None else x1.shape[1]
 
@@ -347,6 +371,15 @@ class Plan:
                 wh = self.stem_weight(stem_w, pack)
                 self.keep += [d, x, wh, bias, out]
                 self._emit(fn, C.byref(d), _ptr(x), _ptr(wh), _ptr(bias), _ptr(out))
+                return out
+        if self.gemm_split and gemm_w is not None and x1 is None and residual is None and not gn_groups:
+            # (a conv whose GroupNorm sums the fp32 epilogue could carry, one with a residual or a second input, and one that
+            # sdc_conv_splitk would take, keep the usual path: conv_gemm_x3_kernel has none of these forms)
+            d = conv_desc(x, None, out, None, cout, k, stride, pad, up, up_mode, 0)
+            if self.lib.sdc_conv_gemm_x3_ok(C.byref(d)) and not (self.split_small_grids and self.lib.sdc_conv_splitk_bytes(C.byref(d))):
+                wb = self.packed(lambda: pack_gemm_x3(gemm_w(), cout, c0, k))
+                self.keep += [d, x, wb, bias, out]
+                self._emit(self.lib.sdc_conv_gemm_x3, C.byref(d), _ptr(x), _ptr(wb), _ptr(bias), _ptr(out))
                 return out
         if callable(wp):
             wp = wp()
@@ -383,7 +416,13 @@ class Plan:
         out = self.pool.get((B, cout, iD, 2 * iH, 2 * iW))
         for ph in (0, 1):
             for pw in (0, 1):
-                wp = self.conv_weight(w, ("convT_sub", ph, pw))
+                kind = ("convT_sub", ph, pw)
+                if self.gemm_split:
+                    # (the usual buffer is packed only if the parity takes the usual path)
+                    self.conv(x, lambda kind=kind: self.conv_weight(w, kind), bias, cout, (1, 2, 2), pad=(0, 1 - ph, 1 - pw),
+                              out=out[:, :, :, ph::2, pw::2], gemm_w=lambda kind=kind: pack_conv_weight(w() if callable(w) else w, kind, 0))
+                    continue
+                wp = self.conv_weight(w, kind)
                 self.conv(x, wp, bias, cout, (1, 2, 2), pad=(0, 1 - ph, 1 - pw), out=out[:, :, :, ph::2, pw::2])
         return out
 

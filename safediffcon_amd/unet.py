@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from ._lib import check, get_lib
-from .engine import Plan, as5
+from .engine import Plan, as5, pack_conv_weight
 
 HEADS, DIM_HEAD = 4, 32
 HID = HEADS * DIM_HEAD
@@ -231,6 +231,11 @@ class _Builder:
             # usual buffer only if not
             return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up, residual=residual,
                                   out=out, gn_groups=gn_groups, stem_w=lambda: self.net.P(wkey))
+        if self.plan.gemm_split and kind == "conv" and k in ((1, 4, 4), (1, 1, 1)) and x1 is None and residual is None:
+            # net.gemm_split: a strided or 1x1 conv; Plan.conv asks the library's routing table and packs the usual buffer only if the
+            # conv stays on the fp32 kernels
+            return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, stride=stride, pad=pad, up=up, out=out, gn_groups=gn_groups,
+                                  gemm_w=lambda: pack_conv_weight(self.net.P(wkey), kind, 0))
         return self.plan.conv(x, self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up,
                               up_mode=1 if kind == "convT" else 0, residual=residual, out=out, gn_groups=gn_groups)
 
@@ -324,6 +329,12 @@ class _HipUNet(nn.Module):
         # both are set, and forward_train, GraphedLossStep and the differentiable DDIM step never see it.  False = conv_rh_kernel
         # (A/B checks).  Read when a plan is built (plans are cached per value).
         self.stem_split = True
+        # the strided (1,4,4)/(1,2,2) convs, the 1x2x2 sub-pixel convs of the transposed convs and the 1x1x1 convs of the sampler plans at
+        # precision >= 4 (default on) as the same exact three-way bf16 splits (conv_gemm_x3_kernel), for the shapes that the library's
+        # measured routing table lists (sdc_conv_gemm_x3_ok; per-sample sizes only, so a sample's bits do not depend on its batch).
+        # fp32-grade like stem_split; precision 0, 2 and 3, forward_train, GraphedLossStep, the differentiable DDIM step, split-K convs
+        # and the conditioning MLP never see it.  False = the fp32 kernels (A/B checks).  Read when a plan is built.
+        self.gemm_split = True
         # LinearAttention blocks of width 64 / 128 as the fused 3-launch form (csrc/sdc_lablock.hip); False = the
         # unfused chain norm -> 1x1 -> attention core -> 1x1 -> norm (kept for wider layers and for A/B checks)
         self.fuse_linattn = True
@@ -486,7 +497,7 @@ class _HipUNet(nn.Module):
         (lut=False, forward(x, time)) or one row per timestep read through a device-side t (lut=True, samplers)."""
         key = (tuple(shape), rows, bool(lut), int(self.precision), bool(self.fuse_linattn), bool(self.subpixel_upsample),
                bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16),
-               bool(self.stem_split))
+               bool(self.stem_split), bool(self.gemm_split))
         stamp = self._weights_stamp()
         ent = self._plans.get(key)
         if ent is not None and ent["wstamp"] != stamp:        # parameters changed since this plan packed them
@@ -496,7 +507,8 @@ class _HipUNet(nn.Module):
             if dev.type != "cuda":
                 raise RuntimeError("safediffcon_amd runs on MI355X only: move the model to a cuda (HIP) device; "
                                    "there is no CPU fallback")
-            plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16), stem_split=bool(self.stem_split))
+            plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16), stem_split=bool(self.stem_split),
+                        gemm_split=bool(self.gemm_split))
             plan.split_small_grids = bool(self.split_small_grids)
             x = torch.zeros(shape, dtype=torch.float32, device=dev)
             eps = torch.zeros(shape, dtype=torch.float32, device=dev)

@@ -18,6 +18,11 @@
   python tools/f16_step.py --split [--workloads c4,c2] [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
       net.stem_split (csrc/sdc_conv_stem_x3.hip, default on): the same stem launches, today's fp32 kernel against sdc_conv_stem_x3 (the
       medians of three interleaved repeats, so that their spread shows); then the C4 sampler step with the switch off against on
+  python tools/f16_step.py --gemm [--workloads c4,c2,c3] [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
+      net.gemm_split (csrc/sdc_conv_gemm_x3.hip, default on): every conv of the nets' forward plans that conv_gemm_x3_kernel covers
+      (strided (1,4,4), sub-pixel (1,2,2), 1x1x1; routed or not), sdc_conv at precision 4 against sdc_conv_gemm_x3 on the same buffers, the
+      medians of 20 launches in three interleaved repeats -- the data of the routing table (sdc_conv_gemm_x3_ok, DESIGN section 15: a
+      shape qualifies when every repeat beats every repeat of the fp32 kernel); then the C4 sampler step with the switch off against on
 """
 import _libsel  # noqa: F401  (SDC_LIB_PATH -> safediffcon_amd._lib.use_library, tools only)
 import argparse
@@ -40,7 +45,7 @@ DEV = torch.device("cuda:0")
 
 def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
     """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16, 'P-nosplit' precision P with
-    net.stem_split off (default: 4 against `arm`)"""
+    net.stem_split off, 'P-nogemm' precision P with net.gemm_split off (default: 4 against `arm`)"""
     torch.cuda.set_device(DEV)
     side = torch.cuda.Stream(device=DEV)
     arms = list(arms or (4, arm))
@@ -53,6 +58,7 @@ def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
                 W = bench.workload(name, None, B, DEV, 0, 1, precision=int(tag.split("+")[0].split("-")[0]), cal_steps=0)
                 W["gd"].model.stem_f16 = tag.endswith("+stem")          # (read when prep() builds the sampler's plan)
                 W["gd"].model.stem_split = not tag.endswith("-nosplit")
+                W["gd"].model.gemm_split = not tag.endswith("-nogemm")
                 torch.manual_seed(2)
                 S = W["prep"]()
                 S.init()
@@ -220,6 +226,71 @@ def stem_shapes(names, split=False):
         torch.cuda.empty_cache()
 
 
+def gemm_shapes(names):
+    """every conv of the switch-off forward plans that sdc_conv_gemm_x3 accepts: today's kernel against it, same buffers"""
+    from safediffcon_amd.engine import pack_gemm_x3
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    nets = {
+        "c4": (lambda: sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7), (64, 32, 7, 64, 64)),
+        "c2": (lambda: sdc.Unet2D(dim=64, dim_mults=(1, 2, 4, 8), channels=3, resnet_block_groups=1), (256, 3, 16, 128)),
+        "c3": (lambda: sdc.Unet1D(dim=256, dim_mults=(1, 2, 4, 8), channels=12, resnet_block_groups=1), (128, 12, 128)),
+    }
+    name_buf = C.create_string_buffer(96)
+    share = C.c_double(0.0)
+    for wl in names:
+        make, shape = nets[wl]
+        torch.manual_seed(0)
+        net = make().to(DEV)
+        net.gemm_split = False
+        x = torch.randn(shape, device=DEV) * 0.5
+        t = torch.full((shape[0],), 500, device=DEV, dtype=torch.long)
+        with torch.no_grad():
+            net(x, t)
+            plan = net.entry(tuple(shape), shape[0])["plan"]
+        by_ptr = {k.data_ptr(): k for k in plan.keep if isinstance(k, torch.Tensor)}
+        seen, tot4, totx, totq = {}, 0.0, 0.0, 0.0
+        for fn, args in plan.calls:
+            if fn.__name__ != "sdc_conv":
+                continue
+            d = args[0]._obj
+            if (d.kH, d.kW) not in ((4, 4), (2, 2), (1, 1)) or d.Cin1 or d.rs[1] or d.Cout % 64:
+                continue
+            key = (d.kH, d.kW, d.sH, d.pH, d.pW, d.Cin0, d.Cout, d.oD, d.oH, d.oW)
+            ncb = {4: 1, 2: 2, 1: 4}[d.kH]
+            if d.Cin0 % (16 * ncb) or int(lib.sdc_pack_gemm_x3_bytes(d.Cout, d.Cin0, d.kH, d.kW)) == 0:
+                continue
+            wp = by_ptr[args[3]]
+            wb = pack_gemm_x3(wp[:d.kH * d.kW * d.Cin0 * d.Cout].reshape(-1, d.Cout), d.Cout, d.Cin0, (d.kH, d.kW)).to(DEV)
+            y4 = torch.empty(d.B * d.Cout * d.oD * d.oH * d.oW * 4 + 64, device=DEV)        # (a parity view spans 4x its elements)
+            rc = lib.sdc_conv_gemm_x3(C.byref(d), args[1], wb.data_ptr(), args[4], y4.data_ptr(), stream)
+            if rc != 0:
+                print(f"{wl} {d.kH}x{d.kW} Cin {d.Cin0} Cout {d.Cout} {d.oD}x{d.oH}x{d.oW}: not covered ({_lib.last_error()})", flush=True)
+                continue
+            lib.sdc_conv_describe(C.byref(d), name_buf, 96, C.byref(share))
+            m4, mx = [], []
+            for _ in range(3):      # interleaved repeats of the median of 20: their spread is what a gain has to beat
+                m4.append(_time_call(lib.sdc_conv, (C.byref(d), args[1], 0, args[3], args[4], 0, y4.data_ptr()), stream))
+                mx.append(_time_call(lib.sdc_conv_gemm_x3, (C.byref(d), args[1], wb.data_ptr(), args[4], y4.data_ptr()), stream))
+            flop = 2.0 * d.B * d.oD * d.oH * d.oW * d.Cout * d.Cin0 * d.kH * d.kW
+            a4, ax = statistics.median(m4), statistics.median(mx)
+            q = max(mx) < min(m4)
+            tot4 += a4
+            totx += ax
+            totq += ax if q else a4
+            seen[key] = seen.get(key, 0) + 1
+            print(f"[measured] {wl} {d.kD}x{d.kH}x{d.kW} stride {d.sH} pad {d.pH},{d.pW} Cin {d.Cin0} Cout {d.Cout} B {d.B} {d.oD}x{d.oH}x{d.oW}: "
+                  f"today {name_buf.value.decode()} {' / '.join(f'{v * 1e3:.1f}' for v in m4)} us ({flop / a4 / 1e9:.0f} TFLOP/s) | "
+                  f"conv_gemm_x3_kernel {' / '.join(f'{v * 1e3:.1f}' for v in mx)} us ({flop / ax / 1e9:.0f} TFLOP/s direct-form) -> x{a4 / ax:.2f} "
+                  f"{'QUALIFIES' if q else 'stays'}; table says {int(lib.sdc_conv_gemm_x3_ok(C.byref(d)))}"
+                  f"{' (repeat)' if seen[key] > 1 else ''}", flush=True)
+            del y4, wb
+        print(f"[measured] {wl}: the covered convs of one forward: fp32 kernels {tot4:.2f} ms, split {totx:.2f} ms, "
+              f"qualifying ones routed {totq:.2f} ms", flush=True)
+        del net, plan, by_ptr
+        torch.cuda.empty_cache()
+
+
 def drift(T, stem=False):
     torch.manual_seed(0)
     net = sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7).to(DEV)
@@ -252,11 +323,16 @@ if __name__ == "__main__":
     ap.add_argument("--drift", type=int, nargs="?", const=1000, default=None)
     ap.add_argument("--stem", action="store_true", help="net.stem_f16: the stem launch and the C4 step (with --drift: the stem arms)")
     ap.add_argument("--split", action="store_true", help="net.stem_split: the stem launch and the C4 step with the switch off / on")
-    ap.add_argument("--no-step", action="store_true", help="--stem / --split: the per-shape part only")
+    ap.add_argument("--gemm", action="store_true", help="net.gemm_split: the covered convs, launch by launch, and the C4 step with the switch off / on")
+    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
         drift(a.drift, a.stem)
+    elif a.gemm:
+        gemm_shapes(wls)
+        if not a.no_step:
+            step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=["4-nogemm", 4])
     elif a.split:
         stem_shapes([w for w in wls if w != "c3"], split=True)
         if not a.no_step:

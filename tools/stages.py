@@ -51,6 +51,15 @@ def classify(lib, fn, a):
         return dict(stage=f"conv {d.kD}x{d.kH}x{d.kW} [stem, bf16 split: exact 3-way operand splits on the bf16 matrix pipe]",
                     kernel="conv_stem_x3_kernel", flops=2.0 * P * d.Cout * d.Cin0 * taps, issued=0.0,
                     bytes=4.0 * (d.B * d.Cin0 * d.iD * d.iH * d.iW + P * d.Cout + taps * d.Cin0 * d.Cout))
+    if fn is lib.sdc_conv_gemm_x3:
+        # (d, x, wb, bias, y): booked like the split stem -- direct-form FLOP, no fp32-MFMA issue (six bf16 MFMAs per product on the
+        # other pipe: 3x the direct-form FLOP as bf16 issue)
+        d = a[0]._obj
+        P, taps = d.B * d.oD * d.oH * d.oW, d.kD * d.kH * d.kW
+        kind = f"conv {d.kD}x{d.kH}x{d.kW}" + (" s2" if d.sH > 1 else "")
+        return dict(stage=f"{kind} [bf16 split: exact 3-way operand splits on the bf16 matrix pipe]",
+                    kernel="conv_gemm_x3_kernel", flops=2.0 * P * d.Cout * d.Cin0 * taps, issued=0.0,
+                    bytes=4.0 * (d.B * d.Cin0 * d.iD * d.iH * d.iW + P * d.Cout + taps * d.Cin0 * d.Cout))
     if fn is lib.sdc_gn_finalize:
         return dict(stage="groupnorm stats (finalize of the conv-epilogue sums)", kernel="gn_finalize", flops=0.0, issued=0.0, bytes=0.0)
     if fn is lib.sdc_gn_stats:

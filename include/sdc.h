@@ -239,6 +239,30 @@ int sdc_tattn_block(const float* x, const float* g_pre, const float* wqkv, const
                     const float* bias, float* y, int outer, int inner, int C, int ntok, int64_t so, int64_t sc,
                     int64_t st, float eps, void* stream);
 
+/* The same block with fp16 operands and fp32 accumulation (net.attn_f16, opt-in, samplers only; DESIGN.md section 16;
+ * csrc/sdc_tablock_f16.hip).  A switch of its own: sdc_tattn_block and its buffers are untouched.  fp32: LayerNorm, rotary, bias,
+ * softmax (maximum, exponent, row sum, division), every accumulator, the residual add.  Rounded once to fp16 (nearest even) as
+ * operands of v_mfma_f32_32x32x16_f16: xn, the weights (at pack time), q and k after the rotary (unscaled), v, the un-normalised
+ * probabilities exp(s - max), O after the division by the row sum.  An operand beyond 65504 becomes infinite.
+ *
+ * Weight buffer (sdc_pack_tattn_f16_bytes() = 65536 bytes, 16-byte aligned), from the nn.Linear weights to_qkv Wqkv (384, 64)
+ * -- rows mat * 128 + head * 32 + d, mat = 0 q, 1 k, 2 v -- and to_out Wo (64, 128).  Every operand fetch of a lane (l31 = lane & 31,
+ * lh = lane >> 5) is one contiguous 16-byte read of 8 fp16 values j = 0 .. 7:
+ *   Wh[head][mat][s][lane][j]       = Wqkv[mat * 128 + head * 32 + l31][16 s + 8 lh + j]           s < 4   (24576 values), then
+ *   Wh'[head][i][s][lane][j]        = Wo[32 i + l31][head * 32 + row(8 s + j, lh)]                 i < 2, s < 2   (8192 values)
+ * with row(r, lh) = (r & 3) + 8 (r >> 2) + 4 lh, the accumulator row that register r of a 32x32 MFMA result holds on half-wave lh:
+ * the kernel's O^T operand arrives in that order.
+ * sdc_pack_tattn_f16 writes the buffer on the device, one launch on `stream` (SDC_ENULL for a null pointer, SDC_EALIGN for a
+ * misaligned dst).
+ *
+ * sdc_tattn_block_f16: arguments, strides, tables and checks of sdc_tattn_block with wpk in place of (wqkv, wo); SDC_ENULL for a
+ * null x, g_pre, wpk or y, SDC_EINVAL for another shape, SDC_EALIGN for a wpk that is not 16-byte aligned, all before any launch.
+ * No atomics, fixed accumulation order; a sample's output does not depend on the batch. */
+size_t sdc_pack_tattn_f16_bytes(void);
+int sdc_pack_tattn_f16(const float* wqkv, const float* wo, void* dst, void* stream);
+int sdc_tattn_block_f16(const float* x, const float* g_pre, const void* wpk, const float* rot, const float* bias, float* y,
+                        int outer, int inner, int C, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream);
+
 /* ------------------------------------------------------- softmax attention */
 /* Attention core (heads x 32): out = softmax(q*scale . k^T + bias) v, optional rotary on q,k.
  * 1D/model/unet.py:247-251 ; conv3d.py:313-353 (focus_present_mask all-False).

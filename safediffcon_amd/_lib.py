@@ -86,6 +86,10 @@ SIGNATURES = {
                                        C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_float, _stream]),
     "sdc_tattn_block": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                   _i64, _i64, _i64, C.c_float, _stream]),
+    "sdc_pack_tattn_f16_bytes": (C.c_size_t, []),
+    "sdc_pack_tattn_f16": (C.c_int, [_f32p, _f32p, C.c_void_p, _stream]),
+    "sdc_tattn_block_f16": (C.c_int, [_f32p, _f32p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      _i64, _i64, _i64, C.c_float, _stream]),
     "sdc_attn": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64,
                            _i64, _i64, _i64, _i64, _stream]),
     "sdc_act": (C.c_int, [_f32p, _f32p, _i64, C.c_int, _stream]),

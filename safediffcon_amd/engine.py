@@ -164,6 +164,21 @@ def pack_stem_x3(w):
     return torch.stack(split3_bf16(z)).reshape(-1).view(torch.float32)
 
 
+def pack_tattn_f16(wqkv, wo):
+    """fp16 buffer of the temporal-attention weights for sdc_tattn_block_f16 (include/sdc.h; host twin of sdc_pack_tattn_f16, bit for
+    bit) from the nn.Linear weights to_qkv (384, 64) and to_out (64, 128), rounded to fp16 (RNE): every operand fetch of a lane (l31 =
+    lane & 31, lh = lane >> 5) is 8 contiguous values j -- Wh[head][mat][s][lane][j] = Wqkv[mat * 128 + head * 32 + l31][16 s + 8 lh + j]
+    (s < 4), then Wh'[head][i][s][lane][j] = Wo[32 i + l31][head * 32 + row(8 s + j, lh)] (i < 2, s < 2) with row(r, lh) = (r & 3) +
+    8 (r >> 2) + 4 lh, the accumulator-row order of a 32x32 MFMA result; returned as the float32 words that hold it"""
+    wqkv, wo = wqkv.to(torch.float32), wo.to(torch.float32)
+    if tuple(wqkv.shape) != (384, 64) or tuple(wo.shape) != (64, 128):
+        raise ValueError(f"pack_tattn_f16: to_qkv (384, 64) and to_out (64, 128) (got {tuple(wqkv.shape)}, {tuple(wo.shape)})")
+    a = wqkv.reshape(3, 4, 32, 4, 2, 8).permute(1, 0, 3, 4, 2, 5)                   # [mat][head][d][s][lh][j] -> [head][mat][s][lh][d][j]
+    # row(8 s + 4 jh + jl, lh) = 16 s + 8 jh + 4 lh + jl: the permutation is a transposition of index digits (no index tensor)
+    b = wo.reshape(2, 32, 4, 2, 2, 2, 4).permute(2, 0, 3, 5, 1, 4, 6)               # [i][l31][head][s][jh][lh][jl] -> [head][i][s][lh][l31][jh][jl]
+    return torch.cat([a.reshape(-1), b.reshape(-1)]).half().view(torch.float32)
+
+
 def pack_gemm_x3(wp, cout, cin, k):
     """bf16 buffer of a strided (1,4,4), sub-pixel (1,2,2) or 1x1x1 conv weight for sdc_conv_gemm_x3 (include/sdc.h; host twin of
     sdc_pack_gemm_x3, bit for bit) from the conv's Wp [taps * Cin][Cout] (pack_conv_weight at precision 0; for a sub-pixel conv the merged
@@ -249,7 +264,7 @@ class Pool:
 class Plan:
     """Recorded kernel calls; `run(stream)` replays them (the samplers capture that replay into a hipGraph)."""
 
-    def __init__(self, device, precision=0, stem_f16=False, stem_split=False, gemm_split=False):
+    def __init__(self, device, precision=0, stem_f16=False, stem_split=False, gemm_split=False, attn_f16=False):
         self.device = torch.device(device)
         self.lib = _lib.get_lib()
         # conv algorithm (include/sdc.h): 0 direct fp32 MFMA | 2 fp32 Winograd F(2,3) along W | 3 F(2x2,3x3) over (H, W) where
@@ -273,6 +288,10 @@ class Plan:
         # conv_gemm_x3_kernel (csrc/sdc_conv_gemm_x3.hip: the stem_split arithmetic) and measured faster than the fp32 kernel -- run it on
         # their pack_gemm_x3 buffer.  Precision 0, 2 and 3 keep the literal fp32 pipe
         self.gemm_split = bool(gemm_split) and self.precision >= 4
+        # net.attn_f16 (opt-in, samplers only, at any precision): the fused temporal-attention block (Plan.tattn_block) runs
+        # ta_block_f16_kernel (fp16 operands, fp32 accumulation; csrc/sdc_tablock_f16.hip) on a buffer of its own (pack_tattn_f16);
+        # everything else, and every call with the switch off, is recorded exactly as without it
+        self.attn_f16 = bool(attn_f16)
         self.calls = []          # (fn, args, keepalive)
         self.pool = Pool(self.device)
         self.keep = []           # descriptors / tensors that must outlive the plan
@@ -550,11 +569,24 @@ class Plan:
                    _ptr(y), outer, inner, Cc, n, *strides, pre_mode, post_mode, eps)
         return y
 
+    def tattn_weight(self, wqkv, wo):
+        """Register the fp16 buffer of the temporal-attention weights (pack_tattn_f16) from the unpacked nn.Linear weights to_qkv / to_out
+        (tensors or callables returning them), refreshed by refresh_weights()."""
+        return self.packed(lambda: pack_tattn_f16(wqkv() if callable(wqkv) else wqkv, wo() if callable(wo) else wo))
+
     def tattn_block(self, x, g_pre, wqkv, wo, rot, bias, eps=1e-5):
-        """Residual(PreNorm(temporal Attention)) of the smoke net in one launch: x (B, 64, 32, H, W) contiguous."""
+        """Residual(PreNorm(temporal Attention)) of the smoke net in one launch: x (B, 64, 32, H, W) contiguous.  wqkv, wo: the packed
+        [64][384] / [128][64] weights (conv_weight); with Plan.attn_f16 the UNPACKED nn.Linear weights to_qkv (384, 64) / to_out (64, 128)
+        (or callables returning them): the call recorded is then sdc_tattn_block_f16 on their pack_tattn_f16 buffer."""
         B, Cc, Fr, H, W = x.shape
         assert x.is_contiguous()
         y = self.pool.get(tuple(x.shape))
+        if self.attn_f16:
+            wpk = self.tattn_weight(wqkv, wo)
+            self.keep += [x, g_pre, wpk, rot, bias, y]
+            self._emit(self.lib.sdc_tattn_block_f16, _ptr(x), _ptr(g_pre), _ptr(wpk), _ptr(rot), _ptr(bias), _ptr(y),
+                       B, H * W, Cc, Fr, Cc * Fr * H * W, Fr * H * W, H * W, eps)
+            return y
         self.keep += [x, g_pre, wqkv, wo, rot, bias, y]
         self._emit(self.lib.sdc_tattn_block, _ptr(x), _ptr(g_pre), _ptr(wqkv), _ptr(wo), _ptr(rot), _ptr(bias), _ptr(y),
                    B, H * W, Cc, Fr, Cc * Fr * H * W, Fr * H * W, H * W, eps)

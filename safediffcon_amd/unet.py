@@ -322,6 +322,13 @@ class _HipUNet(nn.Module):
         # stem, Cin 12, stays fp32).  Works at any `precision`; read when a plan is built, like `precision` (plans are cached per
         # value).  forward_train, GraphedLossStep and the differentiable DDIM step ignore it.
         self.stem_f16 = False
+        # the fused temporal-attention blocks of the sampler plans (width 64, 32 frames: the smoke net's four sites at production width)
+        # on the fp16 matrix pipe (opt-in): xn, the weights, q, k, v, the un-normalised probabilities and O rounded to nearest even as
+        # operands, fp32 accumulation; LayerNorm, rotary, softmax and the residual stay fp32 (ta_block_f16_kernel).  Works at any
+        # `precision`; read when a plan is built (plans are cached per value).  Only the sites that take the fused fp32 block today:
+        # wider layers, the unfused chain (fuse_linattn = False), forward_train, GraphedLossStep and the differentiable DDIM step
+        # ignore it.
+        self.attn_f16 = False
         # the same stem conv of the sampler plans at precision >= 4 (default on): fp32 products formed on the bf16 matrix pipe from
         # exact three-way operand splits (x = bf16 h + m + l, six MFMAs per product, fp32 accumulation; conv_stem_x3_kernel) where it
         # covers the stem (the coverage of stem_f16).  An fp32-grade result in another rounding order, like the Winograd modes -- not a
@@ -497,7 +504,7 @@ class _HipUNet(nn.Module):
         (lut=False, forward(x, time)) or one row per timestep read through a device-side t (lut=True, samplers)."""
         key = (tuple(shape), rows, bool(lut), int(self.precision), bool(self.fuse_linattn), bool(self.subpixel_upsample),
                bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16),
-               bool(self.stem_split), bool(self.gemm_split))
+               bool(self.stem_split), bool(self.gemm_split), bool(self.attn_f16))
         stamp = self._weights_stamp()
         ent = self._plans.get(key)
         if ent is not None and ent["wstamp"] != stamp:        # parameters changed since this plan packed them
@@ -508,7 +515,7 @@ class _HipUNet(nn.Module):
                 raise RuntimeError("safediffcon_amd runs on MI355X only: move the model to a cuda (HIP) device; "
                                    "there is no CPU fallback")
             plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16), stem_split=bool(self.stem_split),
-                        gemm_split=bool(self.gemm_split))
+                        gemm_split=bool(self.gemm_split), attn_f16=bool(self.attn_f16))
             plan.split_small_grids = bool(self.split_small_grids)
             x = torch.zeros(shape, dtype=torch.float32, device=dev)
             eps = torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -784,6 +791,10 @@ class Unet3D_with_Conv3D(_HipUNet):
         hw = H * W
         rot, bias = self._attn_tables(b, F)
         if self.fuse_linattn and C == 64 and F == 32 and hw % 8 == 0 and x.is_contiguous():
+            if plan.attn_f16:
+                # net.attn_f16: the plan packs the fp16 fragment buffer from the unpacked weights
+                return plan.tattn_block(x, b.V(f"{prefix}.fn.norm.gamma"), lambda: self.P(f"{prefix}.fn.fn.fn.to_qkv.weight"),
+                                        lambda: self.P(f"{prefix}.fn.fn.fn.to_out.weight"), rot, bias)
             return plan.tattn_block(x, b.V(f"{prefix}.fn.norm.gamma"), b.W(f"{prefix}.fn.fn.fn.to_qkv.weight"),
                                     b.W(f"{prefix}.fn.fn.fn.to_out.weight"), rot, bias)
         xn = plan.chan_norm(x, b.V(f"{prefix}.fn.norm.gamma"), 0)

@@ -23,6 +23,13 @@
       (strided (1,4,4), sub-pixel (1,2,2), 1x1x1; routed or not), sdc_conv at precision 4 against sdc_conv_gemm_x3 on the same buffers, the
       medians of 20 launches in three interleaved repeats -- the data of the routing table (sdc_conv_gemm_x3_ok, DESIGN section 15: a
       shape qualifies when every repeat beats every repeat of the fp32 kernel); then the C4 sampler step with the switch off against on
+  python tools/f16_step.py --attn [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
+      net.attn_f16 (csrc/sdc_tablock_f16.hip): the fused temporal-attention block at the C4 site shape (64, 64, 32, 64, 64) and at B = 2,
+      sdc_tattn_block against sdc_tattn_block_f16 on the same buffers, the medians of 20 launches in three interleaved repeats (the rule of
+      DESIGN section 15: faster only if every repeat beats every repeat of the fp32 kernel); then the C4 sampler step, precision 4
+      against 4 + attn_f16 and 6 + stem_f16 against 6 + stem_f16 + attn_f16, the four arms interleaved round by round
+  python tools/f16_step.py --drift [T] --attn
+      the T-step guided smoke trajectories with precision 4 + net.attn_f16 against 4
 """
 import _libsel  # noqa: F401  (SDC_LIB_PATH -> safediffcon_amd._lib.use_library, tools only)
 import argparse
@@ -44,8 +51,9 @@ DEV = torch.device("cuda:0")
 
 
 def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
-    """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16, 'P-nosplit' precision P with
-    net.stem_split off, 'P-nogemm' precision P with net.gemm_split off (default: 4 against `arm`)"""
+    """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16, 'P+attn' with net.attn_f16 (both:
+    'P+stem+attn'), 'P-nosplit' precision P with net.stem_split off, 'P-nogemm' precision P with net.gemm_split off (default: 4 against
+    `arm`)"""
     torch.cuda.set_device(DEV)
     side = torch.cuda.Stream(device=DEV)
     arms = list(arms or (4, arm))
@@ -56,7 +64,8 @@ def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
             for prec in arms:
                 tag = str(prec)
                 W = bench.workload(name, None, B, DEV, 0, 1, precision=int(tag.split("+")[0].split("-")[0]), cal_steps=0)
-                W["gd"].model.stem_f16 = tag.endswith("+stem")          # (read when prep() builds the sampler's plan)
+                W["gd"].model.stem_f16 = "+stem" in tag                 # (read when prep() builds the sampler's plan)
+                W["gd"].model.attn_f16 = "+attn" in tag
                 W["gd"].model.stem_split = not tag.endswith("-nosplit")
                 W["gd"].model.gemm_split = not tag.endswith("-nogemm")
                 torch.manual_seed(2)
@@ -291,22 +300,58 @@ def gemm_shapes(names):
         torch.cuda.empty_cache()
 
 
-def drift(T, stem=False):
+def attn_shapes():
+    """the fused temporal-attention block at the C4 site shape and at B = 2: sdc_tattn_block against sdc_tattn_block_f16, same buffers"""
+    from safediffcon_amd.engine import pack_conv_weight, pack_tattn_f16
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    torch.manual_seed(0)
+    wqkv, wo = torch.randn(384, 64, device=DEV) * 0.2, torch.randn(64, 128, device=DEV) * 0.1
+    g = torch.rand(64, device=DEV) + 0.5
+    ang = torch.arange(32, dtype=torch.float32)[:, None] * (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32)))[None, :]
+    rot = torch.stack((ang.cos(), ang.sin()), dim=-1).reshape(-1).to(DEV)
+    bias = torch.randn(4 * 32 * 32, device=DEV) * 0.3
+    wq4, wo4, wpk = pack_conv_weight(wqkv.view(384, 64, 1)), pack_conv_weight(wo.view(64, 128, 1)), pack_tattn_f16(wqkv, wo)
+    for B in (64, 2):
+        x = torch.randn(B, 64, 32, 64, 64, device=DEV) * 0.5
+        y4, yh = torch.empty_like(x), torch.empty_like(x)
+        tail = (B, 64 * 64, 64, 32, 64 * 32 * 64 * 64, 32 * 64 * 64, 64 * 64, 1e-5)
+        a4 = (x.data_ptr(), g.data_ptr(), wq4.data_ptr(), wo4.data_ptr(), rot.data_ptr(), bias.data_ptr(), y4.data_ptr(), *tail)
+        ah = (x.data_ptr(), g.data_ptr(), wpk.data_ptr(), rot.data_ptr(), bias.data_ptr(), yh.data_ptr(), *tail)
+        m4, mh = [], []
+        for _ in range(3):          # interleaved repeats of the median of 20: their spread is what a gain has to beat
+            m4.append(_time_call(lib.sdc_tattn_block, a4, stream))
+            mh.append(_time_call(lib.sdc_tattn_block_f16, ah, stream))
+        br = (y4[:1] - x[:1]).double()
+        err = ((yh[:1] - x[:1]).double() - br).pow(2).mean().sqrt().item() / br.pow(2).mean().sqrt().item()
+        med4, medh = statistics.median(m4), statistics.median(mh)
+        gb = 3.0 * x.numel() * 4 / 1e9
+        print(f"[measured] tattn block B {B} 64 ch 32 frames 64x64: ta_block_kernel {' / '.join(f'{v * 1e3:.1f}' for v in m4)} us | "
+              f"ta_block_f16_kernel {' / '.join(f'{v * 1e3:.1f}' for v in mh)} us ({gb / medh:.2f} TB/s of x read twice + y written) -> "
+              f"x{med4 / medh:.2f} {'FASTER (every repeat beats every repeat)' if max(mh) < min(m4) else 'NOT faster by the rule'}; "
+              f"rms difference of the attention branch on sample 0: {err:.2e}", flush=True)
+        del x, y4, yh
+        torch.cuda.empty_cache()
+
+
+def drift(T, stem=False, attn=False):
     torch.manual_seed(0)
     net = sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7).to(DEV)
     init = (torch.rand(2, 64, 64) * 0.2).to(DEV)
     control = (torch.randn(2, 32, 2, 64, 64) * 0.3).to(DEV)
     outs = {}
-    for prec in ((4, "4+stem", "6+stem") if stem else (4, 6, 7)):
+    arms = (4, "4+attn") if attn else (4, "4+stem", "6+stem") if stem else (4, 6, 7)
+    for prec in arms:
         net.precision = int(prec.split("+")[0]) if isinstance(prec, str) else prec
-        net.stem_f16 = isinstance(prec, str)
+        net.stem_f16 = "+stem" in str(prec)
+        net.attn_f16 = "+attn" in str(prec)
         gs = sdc.GaussianDiffusionSmoke(net, image_size=64, frames=32, timesteps=T, standard_fixed_ratio=100.0).to(DEV)
         torch.manual_seed(7)
         t0 = time.perf_counter()
         outs[prec] = gs.sample(batch_size=2, design_fn=sdc.SmokeGuidance(0.01, 0.9, 0.1), init=init, control=control).cpu()
         print(f"precision {prec}: {time.perf_counter() - t0:.1f} s, finite {bool(torch.isfinite(outs[prec]).all())}, "
               f"|x|max {outs[prec].abs().max():.3f}", flush=True)
-    for p in (("4+stem", "6+stem") if stem else (6, 7)):
+    for p in arms[1:]:
         d = (outs[p] - outs[4]).abs()
         print(f"[measured] {T}-step guided smoke trajectories, precision {p} vs 4: max|diff| {d.max():.3e}  mean|diff| {d.mean():.3e}  "
               f"MSE {(d ** 2).mean():.3e}", flush=True)
@@ -324,11 +369,16 @@ if __name__ == "__main__":
     ap.add_argument("--stem", action="store_true", help="net.stem_f16: the stem launch and the C4 step (with --drift: the stem arms)")
     ap.add_argument("--split", action="store_true", help="net.stem_split: the stem launch and the C4 step with the switch off / on")
     ap.add_argument("--gemm", action="store_true", help="net.gemm_split: the covered convs, launch by launch, and the C4 step with the switch off / on")
-    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm: the per-shape part only")
+    ap.add_argument("--attn", action="store_true", help="net.attn_f16: the block launch and the C4 step (with --drift: 4 + attn_f16 against 4)")
+    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --attn: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
-        drift(a.drift, a.stem)
+        drift(a.drift, a.stem, a.attn)
+    elif a.attn:
+        attn_shapes()
+        if not a.no_step:
+            step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=[4, "4+attn", "6+stem", "6+stem+attn"])
     elif a.gemm:
         gemm_shapes(wls)
         if not a.no_step:

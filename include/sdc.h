@@ -592,6 +592,71 @@ typedef struct {
 } SdcSpan;
 int sdc_checksum_spans(const SdcSpan* spans_dev, int n, uint64_t* out_dev, void* stream);
 
+/* ------------------------------------------------- fine-tuning optimizer step (clip + SGD / Adam / AdamW + EMA) */
+/* The tail of the reference's fine-tuning iteration (1D/inference/inference_ft.py:189-226, 2d/inference_2d.py:261-281):
+ * clip_grad_norm_ -> optimizer.step() -> ema.update(), over EVERY parameter of a net in one streaming pass.
+ *
+ * The caller fills p, g, m, v, ema, n of every item (fp32, n elements each; v null for SGD, ema null without an EMA twin; m, v
+ * and ema are caller-owned and start at zero); sdc_optim_plan (host only, no GPU call) cuts the items into chunks of *chunk
+ * elements, fills chunk0 (the prefix a workgroup searches to find the item of its chunk) and returns the chunk size, the
+ * chunk count and the launch grid (4096 elements; grid = min(total_chunks, 2048), the chunks are grid-strided).  The caller copies the table to device memory and
+ * calls sdc_optim_step(kind, table_dev, ...) per iteration; work holds sdc_optim_bytes(total_chunks) bytes.
+ * Errors of the plan: SDC_ENULL for a null p, g or m, or a null v under Adam / AdamW; SDC_EALIGN for a pointer that is not
+ * 4-byte aligned; SDC_EINVAL for n <= 0 or an unknown kind.  16-byte aligned items take 16-byte loads and stores.
+ *
+ * hp_dev: SDC_OPT_HP_COUNT doubles in device memory (indices below).  state_dev: one SdcOptState in device memory, zeroed by
+ * the caller before the first step.  Everything the step decides -- learning rate, step count, bias corrections, the every-N-th
+ * EMA update, the non-finite skip -- is read from these two, so a captured replay follows the caller's changes of hp_dev.
+ *
+ * One step (t = state.step + 1; element arithmetic in fp32: each a * b + c below is one fused multiply-add, every other operation
+ * is rounded once, nothing else is contracted; sqrt and the division are correctly rounded):
+ *   norm   = sqrt(sum over all items of g^2), per-chunk partial sums in fp64 summed in a fixed order (bit-identical from run
+ *            to run); coef = min(1, max_grad_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); gc = g * coef.
+ *            g ITSELF IS NOT REWRITTEN.  Without SDC_OPT_CLIP coef = 1, and without SDC_OPT_SKIP_NONFINITE as well the norm is
+ *            not computed (state.grad_norm keeps its value).
+ *   SDC_OPT_SKIP_NONFINITE: a NaN / Inf norm leaves p, m, v, ema and state.step untouched (state.applied = 0).
+ *   kind SDC_OPT_SGD    g' = gc + wd p;  m = momentum m + g';  p -= lr m          (dampening 0, no Nesterov)
+ *   kind SDC_OPT_ADAM   g' = gc + wd p;  m += (1 - b1)(g' - m);  v = b2 v + (1 - b2) g'^2;
+ *                       p -= (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps)),  bc = 1 - b^t in fp64
+ *   kind SDC_OPT_ADAMW  p *= 1 - lr wd first, g' = gc, then as Adam
+ *   EMA (items with ema): when t % ema_update_every == 0: t <= ema_update_after_step ? ema = p : ema += (1 - ema_beta)(p - ema)
+ *            with the updated p; on other steps ema is not touched. */
+#define SDC_OPT_SGD 0
+#define SDC_OPT_ADAM 1
+#define SDC_OPT_ADAMW 2
+#define SDC_OPT_CLIP 1
+#define SDC_OPT_SKIP_NONFINITE 2
+#define SDC_OPT_HP_LR 0
+#define SDC_OPT_HP_BETA1 1              /* momentum for SGD */
+#define SDC_OPT_HP_BETA2 2
+#define SDC_OPT_HP_EPS 3
+#define SDC_OPT_HP_WEIGHT_DECAY 4
+#define SDC_OPT_HP_MAX_GRAD_NORM 5
+#define SDC_OPT_HP_EMA_BETA 6
+#define SDC_OPT_HP_EMA_UPDATE_EVERY 7   /* whole numbers stored as doubles; < 1 means never */
+#define SDC_OPT_HP_EMA_UPDATE_AFTER_STEP 8
+#define SDC_OPT_HP_COUNT 9
+typedef struct SdcOptItem {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* ema;
+    int64_t n;
+    int64_t chunk0;           /* filled by sdc_optim_plan: chunks of the items before this one */
+} SdcOptItem;
+typedef struct SdcOptState {
+    int64_t step;             /* steps applied so far */
+    float grad_norm;          /* total gradient 2-norm of the last step that computed it */
+    float clip_coef;          /* the coefficient the last step multiplied the gradients by */
+    int applied;              /* 0: the last step was skipped (SDC_OPT_SKIP_NONFINITE) */
+    int ema_mode;             /* last step: 0 EMA untouched, 1 copied, 2 moving average */
+} SdcOptState;
+int sdc_optim_plan(SdcOptItem* items, int n, int kind, int* chunk, int* total_chunks, int* grid);
+size_t sdc_optim_bytes(int total_chunks);
+int sdc_optim_step(int kind, const SdcOptItem* items_dev, int n, int chunk, int total_chunks, int grid, const double* hp_dev,
+                   SdcOptState* state_dev, void* work, int flags, void* stream);
+
 /* ----------------------------------------------------------------- graphs */
 int sdc_graph_begin(void* stream);
 int sdc_graph_end(void* stream, void** graph_exec);

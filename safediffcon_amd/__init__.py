@@ -8,6 +8,7 @@ Drop-in classes (same names / signatures as the reference):
   control_trajectories (Burgers rollout)                  (safediffcon_amd.solvers)
   KSTARSolver, control_trajectories, evaluate_samples     (safediffcon_amd.kstar: the tokamak score check)
   GraphedLossStep                                         (safediffcon_amd.train_graph: a fine-tuning step as one hipGraph)
+  FusedOptimizer                                          (safediffcon_amd.optim: grad clip + SGD / Adam / AdamW + EMA, three launches)
 
 All compute goes through libsdc_hip.so (include/sdc.h); importing this package
 does not load it, the first kernel call does -- and raises if it is missing.
@@ -17,5 +18,6 @@ from .diffusion import (GaussianDiffusion, GaussianDiffusionBurgers, GaussianDif
                         GaussianDiffusionSmoke, GuidanceSpec, BurgersGuidance, TokamakGuidance, SmokeGuidance,
                         schedule_tables)
 from .train_graph import GraphedLossStep                                               # noqa: F401
+from .optim import FusedOptimizer                                                      # noqa: F401
 
 __version__ = "0.1.0"

@@ -42,6 +42,15 @@ class SdcPackItem(C.Structure):
         ("tap_magic", C.c_uint32), ("_pad", C.c_int32), ("n", C.c_int64 * 5)]
 
 
+class SdcOptItem(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p),
+                ("n", C.c_int64), ("chunk0", C.c_int64)]
+
+
+class SdcOptState(C.Structure):
+    _fields_ = [("step", C.c_int64), ("grad_norm", C.c_float), ("clip_coef", C.c_float), ("applied", C.c_int32), ("ema_mode", C.c_int32)]
+
+
 class SdcSpan(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("nwords", C.c_int64)]
 
@@ -152,6 +161,10 @@ SIGNATURES = {
     "sdc_linear_dgrad": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _i64, _i64, _stream]),
     "sdc_linear_wgrad": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _i64, _i64, _stream]),
     "sdc_checksum_spans": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _stream]),
+    "sdc_optim_plan": (C.c_int, [C.POINTER(SdcOptItem), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sdc_optim_bytes": (C.c_size_t, [C.c_int]),
+    "sdc_optim_step": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                 _stream]),
     "sdc_graph_begin": (C.c_int, [_stream]),
     "sdc_graph_end": (C.c_int, [_stream, C.POINTER(C.c_void_p)]),
     "sdc_graph_launch": (C.c_int, [C.c_void_p, _stream]),

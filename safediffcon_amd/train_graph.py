@@ -21,8 +21,10 @@ class GraphedLossStep:
 
     * ``t`` / ``noise`` None: drawn inside the captured step like ``GaussianDiffusion.forward`` does (torch's Philox state is
       advanced per replay by the graph machinery); given: injected (parity tests).
-    * ``optimizer``: a capturable torch optimizer (e.g. ``torch.optim.Adam(..., capturable=True)``) whose ``step()`` is recorded
-      behind the backward pass; None: the caller steps its optimizer eagerly between replays.
+    * ``optimizer``: a capturable torch optimizer (e.g. ``torch.optim.Adam(..., capturable=True)``) or a ``FusedOptimizer`` (clip,
+      update and EMA twin on the library's kernels) whose ``step()`` is recorded behind the backward pass; None: the caller
+      steps its optimizer eagerly between replays.  A FusedOptimizer's hyper-parameters are uploaded before every replay
+      (``sync_hyperparameters()``), so a scheduler that writes ``param_groups[0]["lr"]`` is followed.
     * ``per_sample`` after a call: the per-sample losses of the step (``diffusion(state, mean=False)``), as the reference's loops log.
     """
 
@@ -51,10 +53,12 @@ class GraphedLossStep:
                 # trained before) is restored from clones: its moments and step counts carry on.
                 with torch.no_grad():
                     saved = [p.detach().clone() for p in params]
+                    twins = list(getattr(optimizer, "ema_params", ()))      # FusedOptimizer.step() updates its EMA twin too
+                    twins_saved = [e.detach().clone() for e in twins]
                     had = {p: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
                            for p, st in optimizer.state.items()}
                     optimizer.step()
-                    for p, q in zip(params, saved):
+                    for p, q in zip(params + twins, saved + twins_saved):
                         p.copy_(q)
                     for p, st in optimizer.state.items():
                         old = had.get(p)
@@ -66,6 +70,8 @@ class GraphedLossStep:
                                     v.zero_()
                             elif old is not None and k in old:
                                 st[k] = old[k]
+            if hasattr(optimizer, "sync_hyperparameters"):
+                optimizer.sync_hyperparameters()     # an upload inside the capture would be replayed with today's values
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         for p in params:
@@ -129,6 +135,8 @@ class GraphedLossStep:
             self.noise.copy_(noise)
         if self.graph is None:
             raise RuntimeError("GraphedLossStep was closed")
+        if hasattr(self.optimizer, "sync_hyperparameters"):
+            self.optimizer.sync_hyperparameters()
         self.graph.replay()
         # an eager optimizer's zero_grad() (set_to_none=True is torch's default, and the reference's loops call it) drops the
         # captured .grad tensors from the parameters: the replay has just written them, seat them again so step() sees them

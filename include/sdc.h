@@ -499,6 +499,42 @@ size_t sdc_pack_gemm_x3_bytes(int Cout, int Cin, int kH, int kW);
 int sdc_pack_gemm_x3(const float* wp, void* out, int Cout, int Cin, int kH, int kW, void* stream);
 int sdc_conv_gemm_x3(const SdcConvDesc* d, const float* x, const void* wb, const float* bias, float* y, void* stream);
 
+/* The 3x3x3 stride-1 convs over rows of 16 as Winograd F(2x2x2,3x3x3) with the Cin products formed from exact three-way bf16 operand
+ * splits on the bf16 matrix pipe (net.wino_split, samplers only; csrc/sdc_conv_wino_x3.hip): precision 4's
+ * algorithm -- the same transforms, passes, folds into the plane pair, bias and GroupNorm epilogue -- with the arithmetic of
+ * sdc_conv_stem_x3: fp32 inputs, fp32 accumulation, fp32 outputs, six v_mfma_f32_32x32x16_bf16 per product (smallest terms first, one
+ * accumulator), fixed k order, no K split, no atomics.  The operands that are split are the transformed ones: V = B^T d B comes out of
+ * the fp32 transform with precision 4's bits and is split as it is staged; U3 is split at pack time.  A switch of its own beside
+ * SdcConvDesc.precision (which these entry points do not read): sdc_conv, its dispatch and every layout above are untouched.
+ *
+ * Covered: what conv_wg3_kernel takes at precision 4 -- 3x3x3 taps, stride 1, pad 1, no upsampling, output size = input size, an even
+ * depth, oH % 16 == 0, Cout % 64 == 0, contiguous input rows, 8-byte aligned rows of y, no residual (rs all zero), one or two
+ * (channel-concatenated) inputs -- with oW == 16 and Cin0 % 16 == 0 and Cin1 % 16 == 0.
+ *
+ * sdc_conv_wino3_x3_ok: 1 where the caller should route the conv here: covered AND measured faster than sdc_conv at precision 4 on the
+ * same buffers (the table in csrc/sdc_conv_wino_x3.hip).  Host only, launches nothing, reads the descriptor only, keyed on per-sample
+ * sizes and never on B.  sdc_conv_wino3_x3 itself accepts every covered descriptor (tests, measurement) and returns SDC_EINVAL for the
+ * others.
+ *
+ * Buffer layout (sdc_pack_wino3_x3_bytes(Cout, Cin) = 3 * 64 * Cin * Cout * 2 bytes, Cin = Cin0 + Cin1, 16-byte aligned; 0 unless
+ * Cout % 64 == 0 and Cin % 16 == 0): three bf16 planes, the exact split h = bf16(u), m = bf16(u - h), l = bf16(u - h - m) (RNE) of
+ * u = U3[jd][ci][co][j * 4 + xi], each Wb[co / 64][jd][stage = ci / 16][j][xi][co % 64][(ci % 16) ^ 8 ((co >> 3) & 1)]: the four
+ * components of a transformed row j of a stage are one contiguous run of 8 KB per plane, and the two channel octets of a row swap
+ * places in rows 8-15 of every 16 (the kernel's fragment reads then cover all LDS banks).  sdc_pack_wino3_x3 writes it on the device, one launch on `stream`, from
+ * the conv's precision-4 buffer wp (sdc_pack_conv_weight at precision 4; U3 is its last part).
+ *
+ * sdc_conv_wino3_x3: y = conv(cat(x, x1), w) + bias (x1, bias may be null), asynchronous on `stream`; y is scratch while the kernel
+ * runs.  gn_parts non-null: the GroupNorm partial sums of sdc_conv_gn for gn_groups groups -- the same table, sized with
+ * sdc_conv_gnparts of the conv at precision 4 -- are written as well; SDC_EINVAL where that says 0.  SDC_ENULL for a null d, x, wb or y
+ * (or x1 with Cin1 > 0), SDC_EINVAL for a descriptor that is not covered, both before any launch; SDC_EALIGN for a wb that is not
+ * 16-byte aligned or an x, x1 or y that is not 8-byte aligned.  Non-finite inputs: the residuals of the split of an infinite value are
+ * inf - inf = NaN, and a plane or row that is clipped away enters as 0 * x: y is NaN where sdc_conv gives an infinity. */
+int sdc_conv_wino3_x3_ok(const SdcConvDesc* d);
+size_t sdc_pack_wino3_x3_bytes(int Cout, int Cin);
+int sdc_pack_wino3_x3(const float* wp, void* out, int Cout, int Cin, void* stream);
+int sdc_conv_wino3_x3(const SdcConvDesc* d, const float* x, const float* x1, const void* wb, const float* bias, float* y,
+                      double* gn_parts, int gn_groups, void* stream);
+
 /* Backward of sdc_gn_apply (GroupNorm -> (scale+1, shift) -> SiLU; Block, conv3d.py:189-204, 1D/model/unet.py:128-147):
  * h = the conv output the forward normalised (contiguous (B,C,S)), stats from the forward, ss = per-sample rows
  * [scale (C) | shift (C)] at ss + b*ss_b_stride or null.  rows: sdc_gn_silu_bwd_floats(B, C, G, S) floats, 8-byte aligned.  Writes

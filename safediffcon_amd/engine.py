@@ -196,6 +196,23 @@ def pack_gemm_x3(wp, cout, cin, k):
     return torch.stack(split3_bf16(z)).reshape(-1).view(torch.float32)
 
 
+def pack_wino3_x3(wp4, cout, cin):
+    """bf16 buffer of a 3x3x3 conv weight for sdc_conv_wino3_x3 (include/sdc.h; host twin of sdc_pack_wino3_x3, bit for bit) from the conv's
+    precision-4 buffer wp4 (pack_conv_weight at precision 4; cin = Cin0 + Cin1), whose last part is U3[jd][ci][co][j * 4 + xi]: three planes
+    Wb[piece][co // 64][jd][ci // 16][j][xi][co % 64][(ci % 16) ^ 8 * ((co >> 3) & 1)] -- the two channel octets of a row swap places in
+    rows 8-15 of every 16 (conflict-free fragment reads) -- holding the exact three-way split of the fp32 Winograd taps (h + m + l == u);
+    returned as the float32 words that hold it"""
+    n = 64 * cin * cout
+    if cout <= 0 or cout % 64 or cin <= 0 or cin % 16 or wp4.dim() != 1 or wp4.numel() != (27 + 36 + 48 + 64) * cin * cout:
+        raise ValueError(f"pack_wino3_x3: Cout % 64 == 0, Cin % 16 == 0, the flat precision-4 buffer of a 3x3x3 conv "
+                         f"(got Cin {cin}, Cout {cout}, {tuple(wp4.shape)})")
+    u3 = wp4[-n:].to(torch.float32).reshape(4, cin // 16, 16, cout // 64, 64, 4, 4)         # [jd][stage][c16][m tile][co][j][xi]
+    # [m tile][jd][stage][j][xi][co / 16][(co / 8) % 2][co % 8][octet][c8]; rows 8-15 of every 16: the octets swapped
+    z = u3.permute(3, 0, 1, 5, 6, 4, 2).reshape(cout // 64, 4, cin // 16, 4, 4, 4, 2, 8, 2, 8)
+    z = torch.stack((z[:, :, :, :, :, :, 0], z[:, :, :, :, :, :, 1].flip(-2)), 6).contiguous()
+    return torch.stack(split3_bf16(z)).reshape(-1).view(torch.float32)
+
+
 def split3_bf16(x):
     """the exact three-way bf16 split of a finite fp32 tensor: (h, m, l) bfloat16 with h + m + l == x (RNE conversions, exact residuals)"""
     h = x.bfloat16()
@@ -264,7 +281,7 @@ class Pool:
 class Plan:
     """Recorded kernel calls; `run(stream)` replays them (the samplers capture that replay into a hipGraph)."""
 
-    def __init__(self, device, precision=0, stem_f16=False, stem_split=False, gemm_split=False, attn_f16=False):
+    def __init__(self, device, precision=0, stem_f16=False, stem_split=False, gemm_split=False, attn_f16=False, wino_split=False):
         self.device = torch.device(device)
         self.lib = _lib.get_lib()
         # conv algorithm (include/sdc.h): 0 direct fp32 MFMA | 2 fp32 Winograd F(2,3) along W | 3 F(2x2,3x3) over (H, W) where
@@ -288,6 +305,11 @@ class Plan:
         # conv_gemm_x3_kernel (csrc/sdc_conv_gemm_x3.hip: the stem_split arithmetic) and measured faster than the fp32 kernel -- run it on
         # their pack_gemm_x3 buffer.  Precision 0, 2 and 3 keep the literal fp32 pipe
         self.gemm_split = bool(gemm_split) and self.precision >= 4
+        # net.wino_split (the nets' switch at precision >= 4, samplers only; off for a Plan built directly): the 3x3x3 convs that
+        # sdc_conv_wino3_x3_ok lists -- covered by conv_wg3_x3_kernel (csrc/sdc_conv_wino_x3.hip: precision 4's Winograd F(2x2x2,3x3x3)
+        # with the stem_split arithmetic) and measured faster than the fp32 kernel -- run it on their pack_wino3_x3 buffer, GroupNorm
+        # sums in the epilogue included.  Precision 0, 2 and 3 keep the literal fp32 pipe, 6 and 7 their fp16 kernels and today's calls
+        self.wino_split = bool(wino_split) and self.precision in (4, 5)
         # net.attn_f16 (opt-in, samplers only, at any precision): the fused temporal-attention block (Plan.tattn_block) runs
         # ta_block_f16_kernel (fp16 operands, fp32 accumulation; csrc/sdc_tablock_f16.hip) on a buffer of its own (pack_tattn_f16);
         # everything else, and every call with the switch off, is recorded exactly as without it
@@ -355,7 +377,7 @@ class Plan:
 
     # ------------------------------------------------------------------ stages
     def conv(self, x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), up_mode=0,
-             residual=None, out=None, gn_groups=0, stem_w=None, gemm_w=None):
+             residual=None, out=None, gn_groups=0, stem_w=None, gemm_w=None, wino_w=None):
         """x (and optional x1, channel-concatenated) are 5-D views; returns out (B,cout,oD,oH,oW).
         gn_groups > 0: a GroupNorm over `out` follows -- where the conv epilogue can sum its statistics (sdc_conv_gn) the
         partial sums are kept for the gn_silu call on `out`, which then skips its own pass over the tensor.
@@ -364,7 +386,10 @@ class Plan:
         Plan.stem_split, where sdc_conv_stem_x3_ok does, sdc_conv_stem_x3 on its pack_stem_x3 buffer; wp may then be a callable,
         packed only when the conv takes the usual path.
         gemm_w: a callable returning the conv's Wp [taps * Cin][Cout] (pack_conv_weight at precision 0): with Plan.gemm_split, where
-        sdc_conv_gemm_x3_ok lists the descriptor, the call recorded is sdc_conv_gemm_x3 on its pack_gemm_x3 buffer (wp as for stem_w)."""
+        sdc_conv_gemm_x3_ok lists the descriptor, the call recorded is sdc_conv_gemm_x3 on its pack_gemm_x3 buffer (wp as for stem_w).
+        wino_w: a callable returning the conv's precision-4 buffer (pack_conv_weight at precision 4): with Plan.wino_split, where
+        sdc_conv_wino3_x3_ok lists the descriptor, the call recorded is sdc_conv_wino3_x3 on its pack_wino3_x3 buffer (wp as for stem_w);
+        with gn_groups its epilogue sums are registered for the gn_silu call on `out` exactly as sdc_conv_gn's are."""
         B, c0, iD, iH, iW = x.shape
         c1 = 0 if x1 is None else x1.shape[1]
 
@@ -399,6 +424,21 @@ class Plan:
                 wb = self.packed(lambda: pack_gemm_x3(gemm_w(), cout, c0, k))
                 self.keep += [d, x, wb, bias, out]
                 self._emit(self.lib.sdc_conv_gemm_x3, C.byref(d), _ptr(x), _ptr(wb), _ptr(bias), _ptr(out))
+                return out
+        if self.wino_split and wino_w is not None and residual is None:
+            # (a conv with a residual, and one that sdc_conv_splitk would take, keep the usual path: conv_wg3_x3_kernel has neither form)
+            d = conv_desc(x, x1, out, None, cout, k, stride, pad, up, up_mode, 4)
+            if self.lib.sdc_conv_wino3_x3_ok(C.byref(d)) and not (self.split_small_grids and self.lib.sdc_conv_splitk_bytes(C.byref(d))):
+                wb = self.packed(lambda: pack_wino3_x3(wino_w(), cout, c0 + c1))
+                self.keep += [d, x, x1, wb, bias, out]
+                nparts = int(self.lib.sdc_conv_gnparts(C.byref(d), gn_groups)) if (gn_groups and self.fuse_gn_stats) else 0
+                parts = None
+                if nparts > 0:
+                    parts = torch.empty(B * gn_groups * nparts * 2, dtype=torch.float64, device=self.device)
+                    self.keep.append(parts)
+                    self._gn_parts[out.data_ptr()] = (parts, nparts, gn_groups)
+                self._emit(self.lib.sdc_conv_wino3_x3, C.byref(d), _ptr(x), _ptr(x1), _ptr(wb), _ptr(bias), _ptr(out), _ptr(parts),
+                           gn_groups if nparts > 0 else 0)
                 return out
         if callable(wp):
             wp = wp()

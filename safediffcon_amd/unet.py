@@ -236,6 +236,11 @@ class _Builder:
             # conv stays on the fp32 kernels
             return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, stride=stride, pad=pad, up=up, out=out, gn_groups=gn_groups,
                                   gemm_w=lambda: pack_conv_weight(self.net.P(wkey), kind, 0))
+        if self.plan.wino_split and kind == "conv" and k == (3, 3, 3) and residual is None:
+            # net.wino_split: a 3x3x3 conv; Plan.conv asks the library's routing table and packs the usual buffer only if the conv stays
+            # on the fp32 kernels
+            return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up, out=out,
+                                  gn_groups=gn_groups, wino_w=lambda: pack_conv_weight(self.net.P(wkey), kind, 4))
         return self.plan.conv(x, self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up,
                               up_mode=1 if kind == "convT" else 0, residual=residual, out=out, gn_groups=gn_groups)
 
@@ -342,6 +347,12 @@ class _HipUNet(nn.Module):
         # fp32-grade like stem_split; precision 0, 2 and 3, forward_train, GraphedLossStep, the differentiable DDIM step, split-K convs
         # and the conditioning MLP never see it.  False = the fp32 kernels (A/B checks).  Read when a plan is built.
         self.gemm_split = True
+        # the 3x3x3 convs of the sampler plans at precision 4 and 5 as Winograd F(2x2x2,3x3x3) with the same exact three-way bf16 splits of
+        # the transformed operands (conv_wg3_x3_kernel), GroupNorm sums in the epilogue included, for the shapes that the library's
+        # measured routing table lists (sdc_conv_wino3_x3_ok; per-sample sizes only).  fp32-grade like stem_split; precision 0, 2, 3, 6 and
+        # 7, forward_train, GraphedLossStep, the differentiable DDIM step, convs with a residual and split-K convs never see it.
+        # False = the fp32 kernels (A/B checks).  Read when a plan is built.
+        self.wino_split = True
         # LinearAttention blocks of width 64 / 128 as the fused 3-launch form (csrc/sdc_lablock.hip); False = the
         # unfused chain norm -> 1x1 -> attention core -> 1x1 -> norm (kept for wider layers and for A/B checks)
         self.fuse_linattn = True
@@ -504,7 +515,7 @@ class _HipUNet(nn.Module):
         (lut=False, forward(x, time)) or one row per timestep read through a device-side t (lut=True, samplers)."""
         key = (tuple(shape), rows, bool(lut), int(self.precision), bool(self.fuse_linattn), bool(self.subpixel_upsample),
                bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16),
-               bool(self.stem_split), bool(self.gemm_split), bool(self.attn_f16))
+               bool(self.stem_split), bool(self.gemm_split), bool(self.attn_f16), bool(self.wino_split))
         stamp = self._weights_stamp()
         ent = self._plans.get(key)
         if ent is not None and ent["wstamp"] != stamp:        # parameters changed since this plan packed them
@@ -515,7 +526,7 @@ class _HipUNet(nn.Module):
                 raise RuntimeError("safediffcon_amd runs on MI355X only: move the model to a cuda (HIP) device; "
                                    "there is no CPU fallback")
             plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16), stem_split=bool(self.stem_split),
-                        gemm_split=bool(self.gemm_split), attn_f16=bool(self.attn_f16))
+                        gemm_split=bool(self.gemm_split), attn_f16=bool(self.attn_f16), wino_split=bool(self.wino_split))
             plan.split_small_grids = bool(self.split_small_grids)
             x = torch.zeros(shape, dtype=torch.float32, device=dev)
             eps = torch.zeros(shape, dtype=torch.float32, device=dev)

@@ -23,6 +23,12 @@
       (strided (1,4,4), sub-pixel (1,2,2), 1x1x1; routed or not), sdc_conv at precision 4 against sdc_conv_gemm_x3 on the same buffers, the
       medians of 20 launches in three interleaved repeats -- the data of the routing table (sdc_conv_gemm_x3_ok, DESIGN section 15: a
       shape qualifies when every repeat beats every repeat of the fp32 kernel); then the C4 sampler step with the switch off against on
+  python tools/f16_step.py --wino [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
+      net.wino_split (csrc/sdc_conv_wino_x3.hip): every 3x3x3 conv of the C4 switch-off plan that conv_wg3_x3_kernel covers (routed or
+      not), sdc_conv / sdc_conv_gn at precision 4 against sdc_conv_wino3_x3 on the same buffers (GroupNorm sums in both where the plan
+      has them), the medians of 20 launches in three interleaved repeats -- the data of the routing table (sdc_conv_wino3_x3_ok, DESIGN
+      section 18: a shape qualifies when every repeat beats every repeat of the fp32 kernel); then the C4 sampler step with the switch
+      off against on
   python tools/f16_step.py --attn [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
       net.attn_f16 (csrc/sdc_tablock_f16.hip): the fused temporal-attention block at the C4 site shape (64, 64, 32, 64, 64) and at B = 2,
       sdc_tattn_block against sdc_tattn_block_f16 on the same buffers, the medians of 20 launches in three interleaved repeats (the rule of
@@ -52,8 +58,8 @@ DEV = torch.device("cuda:0")
 
 def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
     """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16, 'P+attn' with net.attn_f16 (both:
-    'P+stem+attn'), 'P-nosplit' precision P with net.stem_split off, 'P-nogemm' precision P with net.gemm_split off (default: 4 against
-    `arm`)"""
+    'P+stem+attn'), 'P-nosplit' precision P with net.stem_split off, 'P-nogemm' precision P with net.gemm_split off, 'P-nowino' / 'P+wino' precision P
+    with net.wino_split off / on (default: 4 against `arm`)"""
     torch.cuda.set_device(DEV)
     side = torch.cuda.Stream(device=DEV)
     arms = list(arms or (4, arm))
@@ -68,6 +74,8 @@ def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
                 W["gd"].model.attn_f16 = "+attn" in tag
                 W["gd"].model.stem_split = not tag.endswith("-nosplit")
                 W["gd"].model.gemm_split = not tag.endswith("-nogemm")
+                if tag.endswith("-nowino") or "+wino" in tag:
+                    W["gd"].model.wino_split = "+wino" in tag
                 torch.manual_seed(2)
                 S = W["prep"]()
                 S.init()
@@ -300,6 +308,70 @@ def gemm_shapes(names):
         torch.cuda.empty_cache()
 
 
+def wino_shapes():
+    """every 3x3x3 conv of the C4 switch-off forward plan that sdc_conv_wino3_x3 accepts: today's kernel against it, same buffers"""
+    from safediffcon_amd.engine import pack_wino3_x3
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    shape = (64, 32, 7, 64, 64)
+    name_buf = C.create_string_buffer(96)
+    share = C.c_double(0.0)
+    torch.manual_seed(0)
+    net = sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7).to(DEV)
+    net.wino_split = False
+    x = torch.randn(shape, device=DEV) * 0.5
+    t = torch.full((shape[0],), 500, device=DEV, dtype=torch.long)
+    with torch.no_grad():
+        net(x, t)
+        plan = net.entry(tuple(shape), shape[0])["plan"]
+    by_ptr = {k.data_ptr(): k for k in plan.keep if isinstance(k, torch.Tensor)}
+    seen, tot4, totx, totq = {}, 0.0, 0.0, 0.0
+    for fn, args in plan.calls:
+        if fn.__name__ not in ("sdc_conv", "sdc_conv_gn"):
+            continue
+        d = args[0]._obj
+        if (d.kD, d.kH, d.kW) != (3, 3, 3) or args[5] or int(lib.sdc_pack_wino3_x3_bytes(d.Cout, d.Cin0 + d.Cin1)) == 0:
+            continue
+        key = (d.Cin0, d.Cin1, d.Cout, d.oD, d.oH, d.oW, fn.__name__)
+        cin = d.Cin0 + d.Cin1
+        G = args[8] if fn.__name__ == "sdc_conv_gn" else 0
+        nparts = int(lib.sdc_conv_gnparts(C.byref(d), G)) if G else 0
+        parts = torch.empty(max(1, d.B * G * nparts * 2), dtype=torch.float64, device=DEV)
+        y4 = torch.empty(d.B, d.Cout, d.oD, d.oH, d.oW, device=DEV)
+        yx = torch.empty_like(y4)
+        wb = pack_wino3_x3(by_ptr[args[3]].cpu(), d.Cout, cin).to(DEV)
+        ax_args = (C.byref(d), args[1], args[2], wb.data_ptr(), args[4], yx.data_ptr(), parts.data_ptr() if nparts else 0, G if nparts else 0)
+        rc = lib.sdc_conv_wino3_x3(*ax_args, stream)
+        if rc != 0:
+            print(f"c4 3x3x3 Cin {d.Cin0}+{d.Cin1} Cout {d.Cout} {d.oD}x{d.oH}x{d.oW}: not covered ({_lib.last_error()})", flush=True)
+            continue
+        a4_fn = lib.sdc_conv_gn if nparts else lib.sdc_conv
+        a4_args = (C.byref(d), args[1], args[2], args[3], args[4], 0, y4.data_ptr()) + ((parts.data_ptr(), G) if nparts else ())
+        lib.sdc_conv_describe(C.byref(d), name_buf, 96, C.byref(share))
+        m4, mx = [], []
+        for _ in range(3):      # interleaved repeats of the median of 20: their spread is what a gain has to beat
+            m4.append(_time_call(a4_fn, a4_args, stream))
+            mx.append(_time_call(lib.sdc_conv_wino3_x3, ax_args, stream))
+        err = (yx - y4).double().pow(2).mean().sqrt().item() / y4.double().pow(2).mean().sqrt().item()
+        flop = 2.0 * d.B * d.oD * d.oH * d.oW * d.Cout * cin * 27
+        a4, ax = statistics.median(m4), statistics.median(mx)
+        q = max(mx) < min(m4)
+        tot4 += a4
+        totx += ax
+        totq += ax if q else a4
+        seen[key] = seen.get(key, 0) + 1
+        print(f"[measured] c4 3x3x3 Cin {d.Cin0}+{d.Cin1} Cout {d.Cout} B {d.B} {d.oD}x{d.oH}x{d.oW} {fn.__name__}: today {name_buf.value.decode()} "
+              f"{' / '.join(f'{v * 1e3:.1f}' for v in m4)} us ({flop / a4 / 1e9:.0f} TFLOP/s direct-form) | conv_wg3_x3_kernel "
+              f"{' / '.join(f'{v * 1e3:.1f}' for v in mx)} us ({flop / ax / 1e9:.0f} TFLOP/s direct-form, {flop * 8 / 27 * 6 / ax / 1e9:.0f} issued on the "
+              f"bf16 pipe) -> x{a4 / ax:.2f} {'QUALIFIES' if q else 'stays'}; table says {int(lib.sdc_conv_wino3_x3_ok(C.byref(d)))}; "
+              f"rms difference {err:.2e} of the output rms{' (repeat)' if seen[key] > 1 else ''}", flush=True)
+        del y4, yx, wb, parts
+    print(f"[measured] c4: the covered 3x3x3 convs of one forward: fp32 kernels {tot4:.2f} ms, split {totx:.2f} ms, "
+          f"qualifying ones routed {totq:.2f} ms", flush=True)
+    del net, plan, by_ptr
+    torch.cuda.empty_cache()
+
+
 def attn_shapes():
     """the fused temporal-attention block at the C4 site shape and at B = 2: sdc_tattn_block against sdc_tattn_block_f16, same buffers"""
     from safediffcon_amd.engine import pack_conv_weight, pack_tattn_f16
@@ -369,8 +441,9 @@ if __name__ == "__main__":
     ap.add_argument("--stem", action="store_true", help="net.stem_f16: the stem launch and the C4 step (with --drift: the stem arms)")
     ap.add_argument("--split", action="store_true", help="net.stem_split: the stem launch and the C4 step with the switch off / on")
     ap.add_argument("--gemm", action="store_true", help="net.gemm_split: the covered convs, launch by launch, and the C4 step with the switch off / on")
+    ap.add_argument("--wino", action="store_true", help="net.wino_split: the covered 3x3x3 convs, launch by launch, and the C4 step with the switch off / on")
     ap.add_argument("--attn", action="store_true", help="net.attn_f16: the block launch and the C4 step (with --drift: 4 + attn_f16 against 4)")
-    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --attn: the per-shape part only")
+    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --wino / --attn: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
@@ -379,6 +452,10 @@ if __name__ == "__main__":
         attn_shapes()
         if not a.no_step:
             step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=[4, "4+attn", "6+stem", "6+stem+attn"])
+    elif a.wino:
+        wino_shapes()
+        if not a.no_step:
+            step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=["4-nowino", "4+wino"])
     elif a.gemm:
         gemm_shapes(wls)
         if not a.no_step:

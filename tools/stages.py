@@ -60,6 +60,16 @@ def classify(lib, fn, a):
         return dict(stage=f"{kind} [bf16 split: exact 3-way operand splits on the bf16 matrix pipe]",
                     kernel="conv_gemm_x3_kernel", flops=2.0 * P * d.Cout * d.Cin0 * taps, issued=0.0,
                     bytes=4.0 * (d.B * d.Cin0 * d.iD * d.iH * d.iW + P * d.Cout + taps * d.Cin0 * d.Cout))
+    if fn is lib.sdc_conv_wino3_x3:
+        # (d, x, x1, wb, bias, y, parts, G): booked like the other split convs -- direct-form FLOP, no fp32-MFMA issue (the Winograd form
+        # issues 8/27 of the direct products, six bf16 MFMAs each, on the other pipe: 16/9 of the direct-form FLOP as bf16 issue)
+        d = a[0]._obj
+        P, cin = d.B * d.oD * d.oH * d.oW, d.Cin0 + d.Cin1
+        kind = "conv 3x3x3 [Winograd F(2x2x2,3x3x3) over (D,H,W), bf16 split: exact 3-way operand splits on the bf16 matrix pipe]"
+        if a[6]:
+            kind += " + GroupNorm statistics in the epilogue"
+        return dict(stage=kind, kernel="conv_wg3_x3_kernel", flops=2.0 * P * d.Cout * cin * 27, issued=0.0,
+                    bytes=4.0 * (d.B * cin * d.iD * d.iH * d.iW + P * d.Cout + 27 * cin * d.Cout))
     if fn is lib.sdc_gn_finalize:
         return dict(stage="groupnorm stats (finalize of the conv-epilogue sums)", kernel="gn_finalize", flops=0.0, issued=0.0, bytes=0.0)
     if fn is lib.sdc_gn_stats:

@@ -263,6 +263,32 @@ int sdc_pack_tattn_f16(const float* wqkv, const float* wo, void* dst, void* stre
 int sdc_tattn_block_f16(const float* x, const float* g_pre, const void* wpk, const float* rot, const float* bias, float* y,
                         int outer, int inner, int C, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream);
 
+/* The same block with its weight products -- the q / k / v projections and the out-projection -- formed on the bf16 matrix pipe
+ * (v_mfma_f32_32x32x16_bf16) from exact three-way bf16 operand splits, fp32 accumulation (net.attn_split, samplers only, precision 4
+ * and 5; csrc/sdc_tablock_x3.hip).  x = h + m + l with round-to-nearest-even bf16 pieces and exact fp32 residuals;
+ * a product is the six terms a3 b1 + a2 b2 + a1 b3 + a2 b1 + a1 b2 + a1 b1, the small ones first: an fp32-grade result in another
+ * rounding order.  Split: the weights (at pack time), xn (once per tile), O after the softmax normalisation.  fp32 with
+ * sdc_tattn_block's instructions and order: LayerNorm, rotary, bias, the score product, softmax, the O = V P product, every
+ * accumulator, the residual add.  A non-finite x gives NaN where sdc_tattn_block may give an infinity.
+ *
+ * Weight buffer (sdc_pack_tattn_x3_bytes() = 196608 bytes, 16-byte aligned), from the unpacked nn.Linear weights to_qkv (384, 64) and
+ * to_out (64, 128): Wb[head][piece][e], e < 8192, piece 0 / 1 / 2 = h / m / l -- one head's three pieces are one contiguous run of 48 KB.
+ * Position e of a head is sdc_pack_tattn_f16's fragment order restricted to that head:
+ *   e = ((mat * 4 + s) * 64 + lane) * 8 + j          <- Wqkv[mat * 128 + head * 32 + l31][16 s + 8 lh + j]     mat < 3, s < 4, then
+ *   e = 6144 + ((i * 2 + s) * 64 + lane) * 8 + j     <- Wo[32 i + l31][head * 32 + row(8 s + j, lh)]           i < 2, s < 2.
+ * sdc_pack_tattn_x3 writes the buffer on the device, one launch on `stream` (SDC_ENULL for a null pointer, SDC_EALIGN for a
+ * misaligned dst).
+ *
+ * sdc_tattn_block_x3: arguments, strides, tables, checks and error codes of sdc_tattn_block_f16, all before any launch.  No atomics,
+ * fixed accumulation order; a sample's output does not depend on the batch.
+ * sdc_tattn_block_x3_ok: 1 where the routing table of net.attn_split lists the site -- (C, frames, inner = H * W), never B: the sizes
+ * at which the kernel measured faster than sdc_tattn_block in every repeat. */
+size_t sdc_pack_tattn_x3_bytes(void);
+int sdc_pack_tattn_x3(const float* wqkv, const float* wo, void* dst, void* stream);
+int sdc_tattn_block_x3(const float* x, const float* g_pre, const void* wpk, const float* rot, const float* bias, float* y,
+                       int outer, int inner, int C, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream);
+int sdc_tattn_block_x3_ok(int C, int ntok, int inner);
+
 /* ------------------------------------------------------- softmax attention */
 /* Attention core (heads x 32): out = softmax(q*scale . k^T + bias) v, optional rotary on q,k.
  * 1D/model/unet.py:247-251 ; conv3d.py:313-353 (focus_present_mask all-False).

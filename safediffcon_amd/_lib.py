@@ -99,6 +99,11 @@ SIGNATURES = {
     "sdc_pack_tattn_f16": (C.c_int, [_f32p, _f32p, C.c_void_p, _stream]),
     "sdc_tattn_block_f16": (C.c_int, [_f32p, _f32p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                       _i64, _i64, _i64, C.c_float, _stream]),
+    "sdc_pack_tattn_x3_bytes": (C.c_size_t, []),
+    "sdc_pack_tattn_x3": (C.c_int, [_f32p, _f32p, C.c_void_p, _stream]),
+    "sdc_tattn_block_x3": (C.c_int, [_f32p, _f32p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _i64, _i64, _i64, C.c_float, _stream]),
+    "sdc_tattn_block_x3_ok": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "sdc_attn": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64,
                            _i64, _i64, _i64, _i64, _stream]),
     "sdc_act": (C.c_int, [_f32p, _f32p, _i64, C.c_int, _stream]),

@@ -1,0 +1,386 @@
+// net.attn_split (samplers only, precision 4 and 5): the fused temporal-attention block of sdc_tablock.hip with the products that have
+// a weight operand -- the q / k / v projections and the out-projection, 128 of its 160 fp32 MFMAs per head and wave -- formed on the
+// gfx950 bf16 matrix pipe, v_mfma_f32_32x32x16_bf16, from EXACT three-way bf16 operand splits (the arithmetic of conv_stem_x3_kernel):
+//
+//   y = x + Wo . softmax( rot(s Wq xn) rot(Wk xn)^T + relpos ) (Wv xn),   xn = channel LayerNorm(x) * gamma
+//
+//   a = a1 + a2 + a3 (RNE bf16 pieces, exact fp32 residuals);  a b ~ a3 b1 + a2 b2 + a1 b3 + a2 b1 + a1 b2 + a1 b1, fp32 accumulation
+//
+// An fp32-grade result in another rounding order, not a reduced precision.  Walk, tables and exit are ta_block_f16_kernel's (one
+// persistent workgroup per CU, 8 adjacent pixels per tile, one wave per pixel, all 32 frames, all 4 heads, XCD-ordered walk, the next
+// tile's x requested behind the head loop, y out through LDS in two halves).  What is split:
+//   - the weights, once, at pack time (sdc_pack_tattn_x3: three planes in sdc_pack_tattn_f16's fragment order, head by head);
+//   - xn, once per value and tile: the LayerNorm leaves an fp32 image [pixel][frame][channel] in LDS, every wave reads the 32 values of
+//     its lanes' fragments (frame l31, channels 16 s + 8 lh + j) and keeps their three pieces in registers (3 x 16 VGPRs) for all four
+//     heads and both operand roles (B of q and k, A of V^T);
+//   - O^T after the softmax normalisation: eight consecutive accumulator registers are one K fragment, in three pieces.
+// A product's five small terms are issued first, smallest kind first, each over all its K steps, then the main term: one accumulator
+// per output, the main sum rounded K / 16 times.  q, k and V^T are three independent chains.
+// fp32, with ta_block_kernel's instructions and order: LayerNorm, rotary on the accumulators, bias as the start value of the scores, the
+// 32x32x2_f32 score chain from the K and Q registers, softmax, the 32x32x2_f32 O chain from the V^T and P registers (the accumulators
+// of the bf16 MFMA have the fp32 one's register layout), every accumulator, the residual add.
+// LDS (141 KB): weight buffer A (one head, 3 pieces, 48 KB) | region B (68 KB: the fp32 xn image until every wave holds its fragments,
+// then the second weight buffer -- heads 1 and 3 --, then the y halves) | tables.  Head h + 1's weights travel through registers while
+// head h is on the matrix cores; head 3 brings head 0 of the next tile.  One barrier per head.
+// No atomics, fixed accumulation order, a sample's arithmetic does not see the batch.  A non-finite x gives NaN (inf - inf in the
+// residual of the split) where the fp32 kernel may give an infinity.
+#include "sdc_common.h"
+
+namespace {
+
+constexpr int NT = 512;                  // 8 waves: one pixel each, two waves per SIMD
+constexpr int C = 64;
+constexpr int NS = 8;                    // pixels per workgroup
+constexpr int XP = NS * 33;              // pitch of one channel row of the y image: [pixel][33 frames]
+constexpr int XF = 68;                   // pitch (floats) of one token of the xn image: 64 channels + 16 bytes
+constexpr int XPP = 32 * XF + 8;         // pitch (floats) of one pixel of the xn image (+ 32 bytes: the LayerNorm's stores spread over the banks)
+constexpr int WQKV_E = 3 * 4 * 64 * 8;   // bf16 elements of one head's q / k / v fragments (one piece)
+constexpr int HEAD_E = WQKV_E + 2 * 2 * 64 * 8;      // ... of one head (one piece): 8192
+constexpr int WPK_E = 4 * 3 * HEAD_E;    // the whole buffer: [head][piece][HEAD_E]
+constexpr int WBUF_B = 3 * HEAD_E * 2;   // bytes of one head's weights: 49152
+constexpr int REGB_B = NS * XPP * 4;     // bytes of region B: 69888
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float nfloat4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+static_assert(WBUF_B <= REGB_B && 32 * XP * 4 <= REGB_B, "region B holds a head's weights and a y half");
+static_assert(WBUF_B % (16 * NT) == 0, "whole 16-byte words per thread");
+
+struct TaArgs {
+    const float* x; const float* g; const __bf16* wpk; const float* rot; const float* bias;
+    float* y;
+    int inner;               // pixels per outer index (H*W)
+    int nblk;                // pixel groups of NS
+    float eps;
+    int64_t so, sc, st;      // element (o, c, pixel i, frame f) at o*so + c*sc + f*st + i
+};
+
+__host__ __device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+// wave-uniform base (SGPR pair) + 32-bit per-lane byte offset, as in ta_block_kernel
+typedef __attribute__((address_space(1))) float* gptr_t;
+typedef __attribute__((address_space(1))) char* gcptr_t;
+__device__ __forceinline__ gptr_t uni(const float* p) {
+    const uint64_t u = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+    return (gptr_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ float ldu(gptr_t base, uint32_t byte_off) { return *(gptr_t)((gcptr_t)base + byte_off); }
+__device__ __forceinline__ void stu(gptr_t base, uint32_t byte_off, float v) { *(gptr_t)((gcptr_t)base + byte_off) = v; }
+
+// rotary step: x = (x0, x1), cs = (cos, sin) -> (x0 cos - x1 sin, x1 cos + x0 sin) with the roundings of ta_block_kernel's packed pair
+// (a rounded product with the cosine, then one fused multiply-add with the sine), left to the compiler's instruction selection
+typedef float ta2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ ta2 ta_rot(ta2 x, ta2 cs) {
+#pragma clang fp contract(off)
+    const float t0 = x.x * cs.x, t1 = x.y * cs.x;
+    return ta2{__builtin_fmaf(-x.y, cs.y, t0), __builtin_fmaf(x.x, cs.y, t1)};
+}
+
+// x = h + m + l exactly (finite x): hardware RNE conversions, exact fp32 residuals
+__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
+#pragma clang fp contract(off)
+    h = (__bf16)x;
+    const float r = x - (float)h;
+    m = (__bf16)r;
+    l = (__bf16)(r - (float)m);
+}
+
+__global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_x3[];
+    unsigned char* const wA = smem_x3;                                  // [3 pieces][HEAD_E] bf16: heads 0 and 2
+    unsigned char* const rB = smem_x3 + WBUF_B;                         // region B: xn image | heads 1 and 3 | y half
+    float* const xim = reinterpret_cast<float*>(rB);                    // [8 pixels][32 frames][XF] fp32 xn (pixel pitch XPP)
+    float* const ys = reinterpret_cast<float*>(rB);                     // [32][XP] half of the y image
+    float* const biasT = reinterpret_cast<float*>(rB + REGB_B);         // [4][32][33]  [head][key][query]
+    float* const rotcs = biasT + 4 * 32 * 33;                           // [16 m][32 frames][2]: (cos, sin)
+    float* const red = rotcs + 2 * 32 * 16;                             // [2][2][256] LayerNorm partials
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
+    // the walk of ta_block_kernel: workgroup w runs on XCD w & 7; each XCD takes a contiguous eighth of the pixel groups
+    const int nblk = a.nblk, nwg = gridDim.x, w = blockIdx.x;
+    const bool xcd = ((nblk & 7) == 0) && ((nwg & 7) == 0);
+    const int per = xcd ? (nblk >> 3) : nblk;
+    const int base = xcd ? (w & 7) * per : 0;
+    const int first = xcd ? (w >> 3) : w, stride = xcd ? (nwg >> 3) : nwg;
+
+    const int tok = tid & 255, half = tid >> 8, pw = tok & 7, f = tok >> 3;
+    const uint32_t toff = (uint32_t)(((int64_t)f * a.st + pw) * 4);     // this thread's token (byte offset inside one channel of one
+                                                                        // outer index: < 2^32, host check)
+    auto tile_ptr = [&](int li) -> int64_t {
+        const int seq0 = (base + li) * NS;
+        const int o = seq0 / a.inner, i0 = seq0 - o * a.inner;
+        return (int64_t)o * a.so + i0;
+    };
+
+    // one head's weights (three pieces, one contiguous run of 48 KB): six 16-byte words per thread, through registers
+    u32x4 wreg[6];
+    auto fetch_head = [&](int head) {
+        const u32x4* src = reinterpret_cast<const u32x4*>(a.wpk) + head * (WBUF_B / 16) + tid;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) wreg[i] = src[i * NT];
+    };
+    auto park_head = [&](unsigned char* wb) {
+        u32x4* dst = reinterpret_cast<u32x4*>(wb) + tid;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) dst[i * NT] = wreg[i];
+    };
+
+    float v[32];                                   // raw x of the tile about to be normalised (this thread's token, channels half*32 ..)
+    if (first < per) {
+        const float* xt = a.x + tile_ptr(first) + (int64_t)(half * 32) * a.sc;
+#pragma unroll
+        for (int c = 0; c < 32; ++c) v[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
+    }
+    // ---- once per workgroup: head 0's weights, the transposed bias table, the rotary table (the first tile's barriers publish them)
+    {
+        fetch_head(0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int e = tid + i * NT, h = e >> 10, q = (e >> 5) & 31, kk = e & 31;
+            // bias / scale: the q * scale of the reference is applied to the finished scores, inside the softmax's exponent
+            biasT[(h * 32 + kk) * 33 + q] = (a.bias ? a.bias[e] : 0.0f) * 5.65685424949238f;
+        }
+        const float2 rr = a.rot ? *reinterpret_cast<const float2*>(a.rot + tid * 2) : make_float2(1.0f, 0.0f);
+        *reinterpret_cast<float2*>(rotcs + (((tid & 15) * 32) + (tid >> 4)) * 2) = rr;      // tid = frame * 16 + m
+        park_head(wA);
+    }
+    const int hw = wave;                           // this wave's pixel of the tile
+
+    for (int li = first; li < per; li += stride) {
+        const int64_t tp = tile_ptr(li);
+        const bool more = li + stride < per;
+        // ---- 1. LayerNorm over the 64 channels of a token (pixel pw, frame f): two threads per token, 32 channels each (fp32, the
+        //         values of ta_block_kernel)
+        {
+            float sm = 0.f;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) sm += v[c];
+            red[half * 256 + tok] = sm;
+            __syncthreads();
+            const float mean = (red[tok] + red[256 + tok]) * (1.0f / C);
+            float q = 0.f;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) { v[c] -= mean; q += v[c] * v[c]; }
+            red[512 + half * 256 + tok] = q;
+            __syncthreads();
+            const float rstd = rsqrtf((red[512 + tok] + red[768 + tok]) * (1.0f / C) + a.eps);
+            nfloat4* xo = reinterpret_cast<nfloat4*>(xim + pw * XPP + f * XF + half * 32);
+#pragma unroll
+            for (int c4 = 0; c4 < 8; ++c4) {
+                nfloat4 o;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = v[c4 * 4 + j] * rstd * a.g[half * 32 + c4 * 4 + j];
+                xo[c4] = o;
+            }
+        }
+        __syncthreads();                               // xn is in LDS
+        // ---- 2. this wave owns pixel `wave`.  xn fragments: lane (frame l31, half-wave lh), step s holds channels 16 s + 8 lh + j --
+        //         B operand of q and k, A operand of V^T, for every head; split once
+        bf16x8 xf[3][4];
+        {
+            const float* xr = xim + hw * XPP + l31 * XF + 8 * lh;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const nfloat4 lo = *reinterpret_cast<const nfloat4*>(xr + 16 * s), hi = *reinterpret_cast<const nfloat4*>(xr + 16 * s + 4);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    __bf16 ph, pm, pl;
+                    split3(j < 4 ? lo[j] : hi[j - 4], ph, pm, pl);
+                    xf[0][s][j] = ph; xf[1][s][j] = pm; xf[2][s][j] = pl;
+                }
+            }
+        }
+        f32x16 yacc[2];                                // row tiles of y (32 channels each)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) yacc[i][r] = 0.f;
+#pragma unroll 1
+        for (int head = 0; head < 4; ++head) {
+            // the six terms of a product, smallest kind first: weight piece PA[t] with xn / O piece PB[t]
+            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+            const unsigned char* const wh = (head & 1) ? rB : wA;
+            unsigned char* const wn = (head & 1) ? wA : rB;
+            __syncthreads();                           // this head's weights are in LDS; every wave is done with the other buffer (head 0:
+                                                       // with the xn image)
+            const bool next = head < 3 || more;        // (head 3 brings head 0 of the next tile)
+            if (next) fetch_head((head + 1) & 3);
+            const bf16x8* wf = reinterpret_cast<const bf16x8*>(wh) + lane;
+            // q, k [32 d][32 f]: A = W^T fragment, B = xn; V^T [32 f][32 d]: operands swapped, so that its accumulator registers are
+            // the A fragments of O^T = V P as they stand
+            f32x16 q, k, vt;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { q[r] = 0.f; k[r] = 0.f; vt[r] = 0.f; }
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const bf16x8* wp = wf + PA[t] * (HEAD_E / 8);
+                    q = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(0 * 4 + s) * 64], xf[PB[t]][s], q, 0, 0, 0);
+                    k = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(1 * 4 + s) * 64], xf[PB[t]][s], k, 0, 0, 0);
+                    vt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[PB[t]][s], wp[(2 * 4 + s) * 64], vt, 0, 0, 0);
+                    if (s == 3) __builtin_amdgcn_sched_barrier(0);      // (a term's fragment reads stay with the term: no spills)
+                }
+            if (next) park_head(wn);
+            // rotary on (d = 2m, 2m+1) pairs = registers (r, r+1) for even r; frame = l31 (fp32, on the accumulators)
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const int m = crow(r, lh) >> 1;
+                const ta2 cs = *reinterpret_cast<const ta2*>(rotcs + (m * 32 + l31) * 2);
+                ta2 q2 = {q[r], q[r + 1]}, k2 = {k[r], k[r + 1]};
+                q2 = ta_rot(q2, cs);
+                k2 = ta_rot(k2, cs);
+                q[r] = q2.x; q[r + 1] = q2.y;
+                k[r] = k2.x; k[r + 1] = k2.y;
+            }
+            // S^T[key][query] / scale = bias / scale + sum_d K[d][key] Q[d][query]: A = K registers, B = Q registers (fp32 pipe, one
+            // chain that starts from the bias)
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = biasT[(head * 32 + crow(r, lh)) * 33 + l31];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(k[r], q[r], acc, 0, 0, 0);
+            float mx = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc[r]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            // p = exp(scale (acc - mx)) = exp2(acc * (scale log2 e) - mx * (scale log2 e)): one fma + v_exp per element
+            const float SL = 0.17677669529663687f * 1.4426950408889634f;
+            const float nmx = -mx * SL;
+            float sum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc[r] = __builtin_amdgcn_exp2f(fmaf(acc[r], SL, nmx)); sum += acc[r]; }
+            sum += __shfl_xor(sum, 32, 64);
+            const float inv = 1.0f / sum;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] *= inv;
+            // O^T[d][query] = sum_key V^T[key][d] P[key][query]: A = V^T registers, B = P registers (fp32 pipe, one chain)
+            f32x16 oacc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) oacc[r] = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) oacc = __builtin_amdgcn_mfma_f32_32x32x2f32(vt[r], acc[r], oacc, 0, 0, 0);
+            // y[co][f] += sum_d Wo[co][head*32 + d] O^T[d][f]:  A = Wo fragments (d in accumulator-row order), B = the pieces of O^T:
+            // registers 8 s .. 8 s + 7 are one K fragment
+            bf16x8 of[3][2];
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    __bf16 ph, pm, pl;
+                    split3(oacc[8 * s + j], ph, pm, pl);
+                    of[0][s][j] = ph; of[1][s][j] = pm; of[2][s][j] = pl;
+                }
+            const bf16x8* wof = wf + WQKV_E / 8;
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const bf16x8* wp = wof + PA[t] * (HEAD_E / 8);
+                    yacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(0 * 2 + s) * 64], of[PB[t]][s], yacc[0], 0, 0, 0);
+                    yacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(1 * 2 + s) * 64], of[PB[t]][s], yacc[1], 0, 0, 0);
+                }
+        }
+        // ---- 3. the next tile's x is requested, then y leaves in two halves of 32 channels through region B: thread (token, half)
+        //         adds the residual (L2-warm second read of x) to channels i*32 + half*16 .. + 16 and stores them
+        {   // (unconditional: the last tile re-reads itself)
+            const float* xt = a.x + tile_ptr(more ? li + stride : li) + (int64_t)(half * 32) * a.sc;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) v[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float xr[16];
+            const int64_t ch0 = (int64_t)(i * 32 + half * 16) * a.sc;
+            const float* xt = a.x + tp + ch0;
+#pragma unroll
+            for (int c = 0; c < 16; ++c) xr[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
+            __syncthreads();                           // every wave is done with head 3's weights / with the previous half of the y image
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ys[crow(r, lh) * XP + hw * 33 + l31] = yacc[i][r];
+            __syncthreads();
+            const float* yt = a.y + tp + ch0;
+#pragma unroll
+            for (int c = 0; c < 16; ++c) stu(uni(yt + (int64_t)c * a.sc), toff, ys[(half * 16 + c) * XP + pw * 33 + f] + xr[c]);
+        }
+        __syncthreads();                               // the y image is consumed: region B is free for the next tile's xn
+    }
+}
+
+// dst[head][piece][e], e < HEAD_E: the three bf16 pieces of the element that sdc_pack_tattn_f16 puts at fragment position e of the head
+// (include/sdc.h), from the nn.Linear weights to_qkv (384, 64) and to_out (64, 128); one thread per element of a plane
+__global__ __launch_bounds__(256) void pack_tattn_x3_kernel(const float* __restrict__ wqkv, const float* __restrict__ wo,
+                                                            __bf16* __restrict__ dst) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= 4 * HEAD_E) return;
+    const int head = g / HEAD_E, e = g - head * HEAD_E;
+    const int j = e & 7, lane = (e >> 3) & 63, l31 = lane & 31, lh = lane >> 5;
+    float wv;
+    if (e < WQKV_E) {
+        const int s = (e >> 9) & 3, mat = e >> 11;
+        wv = wqkv[(mat * 128 + head * 32 + l31) * C + 16 * s + 8 * lh + j];
+    } else {
+        const int e2 = e - WQKV_E, s = (e2 >> 9) & 1, i = (e2 >> 10) & 1;
+        wv = wo[(32 * i + l31) * 128 + head * 32 + crow(8 * s + j, lh)];
+    }
+    __bf16 ph, pm, pl;
+    split3(wv, ph, pm, pl);
+    __bf16* d = dst + (int64_t)head * 3 * HEAD_E + e;
+    d[0] = ph; d[HEAD_E] = pm; d[2 * HEAD_E] = pl;
+}
+
+// The routing table of net.attn_split: the sites where every repeat of sdc_tattn_block_x3 measured faster than
+// every repeat of sdc_tattn_block on the same buffers (profiles/attn_x3_shapes.log).  Per-sample sizes only, never B.
+bool sdc_tattn_x3_faster(int Cc, int ntok, int inner) {
+    return Cc == 64 && ntok == 32 && inner == 4096;
+}
+
+}  // namespace
+
+extern "C" int sdc_tattn_block_x3_ok(int Cc, int ntok, int inner) { return sdc_tattn_x3_faster(Cc, ntok, inner) ? 1 : 0; }
+
+extern "C" size_t sdc_pack_tattn_x3_bytes(void) { return (size_t)WPK_E * sizeof(__bf16); }
+
+extern "C" int sdc_pack_tattn_x3(const float* wqkv, const float* wo, void* dst, void* stream) {
+    SDC_REQUIRE(wqkv && wo && dst, SDC_ENULL, "sdc_pack_tattn_x3: null pointer");
+    SDC_REQUIRE(reinterpret_cast<uintptr_t>(dst) % 16 == 0, SDC_EALIGN, "sdc_pack_tattn_x3: dst must be 16-byte aligned");
+    hipLaunchKernelGGL(pack_tattn_x3_kernel, dim3(4 * HEAD_E / 256), dim3(256), 0, sdc::as_stream(stream), wqkv, wo,
+                       reinterpret_cast<__bf16*>(dst));
+    return sdc::check_launch("sdc_pack_tattn_x3");
+}
+
+extern "C" int sdc_tattn_block_x3(const float* x, const float* g_pre, const void* wpk, const float* rot, const float* bias, float* y,
+                                  int outer, int inner, int Cc, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream) {
+    SDC_REQUIRE(x && g_pre && wpk && y, SDC_ENULL, "sdc_tattn_block_x3: null pointer");
+    SDC_REQUIRE(Cc == 64 && ntok == 32, SDC_EINVAL, "sdc_tattn_block_x3: dim 64 and 32 frames only (got %d, %d)", Cc, ntok);
+    SDC_REQUIRE(outer > 0 && inner > 0 && inner % NS == 0, SDC_EINVAL, "sdc_tattn_block_x3: pixels per image must be a multiple of 8");
+    const int64_t nblk = (int64_t)outer * inner / NS;
+    SDC_REQUIRE(nblk < (1ll << 31), SDC_EINVAL, "sdc_tattn_block_x3: too many sequences");
+    SDC_REQUIRE(((int64_t)31 * st + inner + (int64_t)63 * sc) * 4 < (1ll << 32) && so >= 0 && sc >= 0 && st >= 0, SDC_EINVAL,
+                "sdc_tattn_block_x3: one outer index must span less than 4 GB (32-bit lane offsets)");
+    // the weight buffer is fetched with 16-byte and the rotary table with 8-byte vector loads
+    SDC_REQUIRE(reinterpret_cast<uintptr_t>(wpk) % 16 == 0, SDC_EALIGN, "sdc_tattn_block_x3: the weight buffer must be 16-byte aligned");
+    SDC_REQUIRE(!rot || reinterpret_cast<uintptr_t>(rot) % 8 == 0, SDC_EINVAL, "sdc_tattn_block_x3: rot must be 8-byte aligned");
+    TaArgs a;
+    a.x = x; a.g = g_pre; a.wpk = reinterpret_cast<const __bf16*>(wpk); a.rot = rot; a.bias = bias; a.y = y;
+    a.inner = inner; a.nblk = (int)nblk; a.eps = eps; a.so = so; a.sc = sc; a.st = st;
+    const size_t ldsb = (size_t)WBUF_B + REGB_B + sizeof(float) * (size_t)(4 * 32 * 33 + 2 * 32 * 16 + 1024);
+    static std::atomic<uint64_t> attr{0};
+    SDC_LDS_OPTIN(attr, ta_block_x3_kernel, 160 * 1024, "sdc_tattn_block_x3");
+    // one persistent workgroup per CU (141 KB of LDS: one fits), at most one per pixel group; the CU count is queried once per device
+    static std::atomic<int> ncu_of[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { sdc::set_error("sdc_tattn_block_x3: hipGetDevice failed"); return SDC_EHIP; }
+    int ncu = ncu_of[dev].load(std::memory_order_acquire);
+    if (ncu <= 0) {
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
+            sdc::set_error("sdc_tattn_block_x3: cannot read the CU count of device %d", dev);
+            return SDC_EHIP;
+        }
+        ncu_of[dev].store(ncu, std::memory_order_release);
+    }
+    const unsigned grid = (unsigned)(nblk < ncu ? nblk : ncu);
+    hipLaunchKernelGGL(ta_block_x3_kernel, dim3(grid), dim3(NT), ldsb, sdc::as_stream(stream), a);
+    return sdc::check_launch("sdc_tattn_block_x3");
+}

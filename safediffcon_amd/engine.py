@@ -179,6 +179,20 @@ def pack_tattn_f16(wqkv, wo):
     return torch.cat([a.reshape(-1), b.reshape(-1)]).half().view(torch.float32)
 
 
+def pack_tattn_x3(wqkv, wo):
+    """bf16 buffer of the temporal-attention weights for sdc_tattn_block_x3 (include/sdc.h; host twin of sdc_pack_tattn_x3, bit for bit)
+    from the nn.Linear weights to_qkv (384, 64) and to_out (64, 128): Wb[head][piece][e], e < 8192 -- position e of a head in
+    pack_tattn_f16's fragment order (its 6144 q / k / v values [mat][s][lane][j], then its 2048 to_out values [i][s][lane][j]), the
+    three planes holding the exact three-way split of the fp32 weight (h + m + l == w); returned as the float32 words that hold it"""
+    wqkv, wo = wqkv.to(torch.float32), wo.to(torch.float32)
+    if tuple(wqkv.shape) != (384, 64) or tuple(wo.shape) != (64, 128):
+        raise ValueError(f"pack_tattn_x3: to_qkv (384, 64) and to_out (64, 128) (got {tuple(wqkv.shape)}, {tuple(wo.shape)})")
+    a = wqkv.reshape(3, 4, 32, 4, 2, 8).permute(1, 0, 3, 4, 2, 5)                   # [mat][head][d][s][lh][j] -> [head][mat][s][lh][d][j]
+    b = wo.reshape(2, 32, 4, 2, 2, 2, 4).permute(2, 0, 3, 5, 1, 4, 6)               # (pack_tattn_f16) -> [head][i][s][lh][l31][jh][jl]
+    z = torch.cat([a.reshape(4, -1), b.reshape(4, -1)], 1)                         # [head][e]
+    return torch.stack(split3_bf16(z), 1).reshape(-1).view(torch.float32)
+
+
 def pack_gemm_x3(wp, cout, cin, k):
     """bf16 buffer of a strided (1,4,4), sub-pixel (1,2,2) or 1x1x1 conv weight for sdc_conv_gemm_x3 (include/sdc.h; host twin of
     sdc_pack_gemm_x3, bit for bit) from the conv's Wp [taps * Cin][Cout] (pack_conv_weight at precision 0; for a sub-pixel conv the merged
@@ -281,7 +295,8 @@ class Pool:
 class Plan:
     """Recorded kernel calls; `run(stream)` replays them (the samplers capture that replay into a hipGraph)."""
 
-    def __init__(self, device, precision=0, stem_f16=False, stem_split=False, gemm_split=False, attn_f16=False, wino_split=False):
+    def __init__(self, device, precision=0, stem_f16=False, stem_split=False, gemm_split=False, attn_f16=False, wino_split=False,
+                 attn_split=False):
         self.device = torch.device(device)
         self.lib = _lib.get_lib()
         # conv algorithm (include/sdc.h): 0 direct fp32 MFMA | 2 fp32 Winograd F(2,3) along W | 3 F(2x2,3x3) over (H, W) where
@@ -314,6 +329,11 @@ class Plan:
         # ta_block_f16_kernel (fp16 operands, fp32 accumulation; csrc/sdc_tablock_f16.hip) on a buffer of its own (pack_tattn_f16);
         # everything else, and every call with the switch off, is recorded exactly as without it
         self.attn_f16 = bool(attn_f16)
+        # net.attn_split (the nets' switch at precision 4 and 5, samplers only; off for a Plan built directly): the fused temporal-
+        # attention sites that sdc_tattn_block_x3_ok lists -- measured faster than the fp32 block -- run ta_block_x3_kernel
+        # (csrc/sdc_tablock_x3.hip: the weight products with the stem_split arithmetic, the rest with the fp32 block's instructions) on
+        # their pack_tattn_x3 buffer.  Every other precision keeps today's calls; attn_f16 wins
+        self.attn_split = bool(attn_split) and self.precision in (4, 5) and not self.attn_f16
         self.calls = []          # (fn, args, keepalive)
         self.pool = Pool(self.device)
         self.keep = []           # descriptors / tensors that must outlive the plan
@@ -609,18 +629,31 @@ class Plan:
                    _ptr(y), outer, inner, Cc, n, *strides, pre_mode, post_mode, eps)
         return y
 
-    def tattn_weight(self, wqkv, wo):
-        """Register the fp16 buffer of the temporal-attention weights (pack_tattn_f16) from the unpacked nn.Linear weights to_qkv / to_out
-        (tensors or callables returning them), refreshed by refresh_weights()."""
-        return self.packed(lambda: pack_tattn_f16(wqkv() if callable(wqkv) else wqkv, wo() if callable(wo) else wo))
+    def tattn_weight(self, wqkv, wo, split=False):
+        """Register the fp16 buffer of the temporal-attention weights (pack_tattn_f16; split: the three bf16 planes of pack_tattn_x3)
+        from the unpacked nn.Linear weights to_qkv / to_out (tensors or callables returning them), refreshed by refresh_weights()."""
+        pack = pack_tattn_x3 if split else pack_tattn_f16
+        return self.packed(lambda: pack(wqkv() if callable(wqkv) else wqkv, wo() if callable(wo) else wo))
+
+    def tattn_split_routes(self, Cc, Fr, hw):
+        """True where net.attn_split sends a fused temporal-attention site of width Cc, Fr frames and hw pixels per sample to
+        sdc_tattn_block_x3: the switch is on and the library's measured routing table lists the site (never the batch)"""
+        return self.attn_split and bool(self.lib.sdc_tattn_block_x3_ok(int(Cc), int(Fr), int(hw)))
 
     def tattn_block(self, x, g_pre, wqkv, wo, rot, bias, eps=1e-5):
         """Residual(PreNorm(temporal Attention)) of the smoke net in one launch: x (B, 64, 32, H, W) contiguous.  wqkv, wo: the packed
         [64][384] / [128][64] weights (conv_weight); with Plan.attn_f16 the UNPACKED nn.Linear weights to_qkv (384, 64) / to_out (64, 128)
-        (or callables returning them): the call recorded is then sdc_tattn_block_f16 on their pack_tattn_f16 buffer."""
+        (or callables returning them): the call recorded is then sdc_tattn_block_f16 on their pack_tattn_f16 buffer.  The same holds
+        for a site that tattn_split_routes() lists: unpacked weights, sdc_tattn_block_x3 on their pack_tattn_x3 buffer."""
         B, Cc, Fr, H, W = x.shape
         assert x.is_contiguous()
         y = self.pool.get(tuple(x.shape))
+        if self.tattn_split_routes(Cc, Fr, H * W):
+            wpk = self.tattn_weight(wqkv, wo, split=True)
+            self.keep += [x, g_pre, wpk, rot, bias, y]
+            self._emit(self.lib.sdc_tattn_block_x3, _ptr(x), _ptr(g_pre), _ptr(wpk), _ptr(rot), _ptr(bias), _ptr(y),
+                       B, H * W, Cc, Fr, Cc * Fr * H * W, Fr * H * W, H * W, eps)
+            return y
         if self.attn_f16:
             wpk = self.tattn_weight(wqkv, wo)
             self.keep += [x, g_pre, wpk, rot, bias, y]

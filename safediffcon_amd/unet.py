@@ -353,6 +353,13 @@ class _HipUNet(nn.Module):
         # 7, forward_train, GraphedLossStep, the differentiable DDIM step, convs with a residual and split-K convs never see it.
         # False = the fp32 kernels (A/B checks).  Read when a plan is built.
         self.wino_split = True
+        # the fused temporal-attention blocks of the sampler plans at precision 4 and 5 with their weight products -- the q / k / v
+        # projections and the out-projection -- as the same exact three-way bf16 splits (ta_block_x3_kernel; the score and O = V P
+        # products, LayerNorm, rotary, softmax and the residual keep the fp32 kernel's instructions), for the sites that the library's
+        # measured routing table lists (sdc_tattn_block_x3_ok; width, frames and pixels per sample, never the batch).  fp32-grade like
+        # stem_split; attn_f16 wins when both are set; every other precision, the unfused chain, forward_train, GraphedLossStep and the
+        # differentiable DDIM step never see it.  False = the fp32 block (A/B checks).  Read when a plan is built.
+        self.attn_split = True
         # LinearAttention blocks of width 64 / 128 as the fused 3-launch form (csrc/sdc_lablock.hip); False = the
         # unfused chain norm -> 1x1 -> attention core -> 1x1 -> norm (kept for wider layers and for A/B checks)
         self.fuse_linattn = True
@@ -515,7 +522,7 @@ class _HipUNet(nn.Module):
         (lut=False, forward(x, time)) or one row per timestep read through a device-side t (lut=True, samplers)."""
         key = (tuple(shape), rows, bool(lut), int(self.precision), bool(self.fuse_linattn), bool(self.subpixel_upsample),
                bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16),
-               bool(self.stem_split), bool(self.gemm_split), bool(self.attn_f16), bool(self.wino_split))
+               bool(self.stem_split), bool(self.gemm_split), bool(self.attn_f16), bool(self.wino_split), bool(self.attn_split))
         stamp = self._weights_stamp()
         ent = self._plans.get(key)
         if ent is not None and ent["wstamp"] != stamp:        # parameters changed since this plan packed them
@@ -526,7 +533,8 @@ class _HipUNet(nn.Module):
                 raise RuntimeError("safediffcon_amd runs on MI355X only: move the model to a cuda (HIP) device; "
                                    "there is no CPU fallback")
             plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16), stem_split=bool(self.stem_split),
-                        gemm_split=bool(self.gemm_split), attn_f16=bool(self.attn_f16), wino_split=bool(self.wino_split))
+                        gemm_split=bool(self.gemm_split), attn_f16=bool(self.attn_f16), wino_split=bool(self.wino_split),
+                        attn_split=bool(self.attn_split))
             plan.split_small_grids = bool(self.split_small_grids)
             x = torch.zeros(shape, dtype=torch.float32, device=dev)
             eps = torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -802,8 +810,8 @@ class Unet3D_with_Conv3D(_HipUNet):
         hw = H * W
         rot, bias = self._attn_tables(b, F)
         if self.fuse_linattn and C == 64 and F == 32 and hw % 8 == 0 and x.is_contiguous():
-            if plan.attn_f16:
-                # net.attn_f16: the plan packs the fp16 fragment buffer from the unpacked weights
+            if plan.attn_f16 or plan.tattn_split_routes(C, F, hw):
+                # net.attn_f16 / a site that net.attn_split routes: the plan packs the fragment buffer from the unpacked weights
                 return plan.tattn_block(x, b.V(f"{prefix}.fn.norm.gamma"), lambda: self.P(f"{prefix}.fn.fn.fn.to_qkv.weight"),
                                         lambda: self.P(f"{prefix}.fn.fn.fn.to_out.weight"), rot, bias)
             return plan.tattn_block(x, b.V(f"{prefix}.fn.norm.gamma"), b.W(f"{prefix}.fn.fn.fn.to_qkv.weight"),

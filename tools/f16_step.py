@@ -36,6 +36,12 @@
       against 4 + attn_f16 and 6 + stem_f16 against 6 + stem_f16 + attn_f16, the four arms interleaved round by round
   python tools/f16_step.py --drift [T] --attn
       the T-step guided smoke trajectories with precision 4 + net.attn_f16 against 4
+  python tools/f16_step.py --attn-split [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
+      net.attn_split (csrc/sdc_tablock_x3.hip): the fused temporal-attention block at the sites of the dim-64 smoke net -- 64 x 64 pixels
+      per sample at B = 64 (the C4 site) and B = 2, 32 x 32 and 16 x 16 at B = 64 --, sdc_tattn_block against sdc_tattn_block_x3 on the same
+      buffers, the medians of 20 launches in three interleaved repeats -- the data of the routing table (sdc_tattn_block_x3_ok, DESIGN
+      section 19: a shape qualifies when every repeat beats every repeat of the fp32 kernel); then the C4 sampler step with the switch
+      off against on
 """
 import _libsel  # noqa: F401  (SDC_LIB_PATH -> safediffcon_amd._lib.use_library, tools only)
 import argparse
@@ -59,7 +65,7 @@ DEV = torch.device("cuda:0")
 def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
     """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16, 'P+attn' with net.attn_f16 (both:
     'P+stem+attn'), 'P-nosplit' precision P with net.stem_split off, 'P-nogemm' precision P with net.gemm_split off, 'P-nowino' / 'P+wino' precision P
-    with net.wino_split off / on (default: 4 against `arm`)"""
+    with net.wino_split off / on, 'P-noasplit' / 'P+asplit' with net.attn_split off / on (default: 4 against `arm`)"""
     torch.cuda.set_device(DEV)
     side = torch.cuda.Stream(device=DEV)
     arms = list(arms or (4, arm))
@@ -74,6 +80,8 @@ def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
                 W["gd"].model.attn_f16 = "+attn" in tag
                 W["gd"].model.stem_split = not tag.endswith("-nosplit")
                 W["gd"].model.gemm_split = not tag.endswith("-nogemm")
+                if tag.endswith("-noasplit") or "+asplit" in tag:
+                    W["gd"].model.attn_split = "+asplit" in tag
                 if tag.endswith("-nowino") or "+wino" in tag:
                     W["gd"].model.wino_split = "+wino" in tag
                 torch.manual_seed(2)
@@ -406,6 +414,43 @@ def attn_shapes():
         torch.cuda.empty_cache()
 
 
+def attn_split_shapes():
+    """net.attn_split: sdc_tattn_block against sdc_tattn_block_x3 on the same buffers at the sites of the dim-64 smoke net -- 64 x 64 (the
+    C4 site, B = 64 and B = 2), 32 x 32 and 16 x 16 (B = 64); the medians of 20 launches, three interleaved repeats; a shape QUALIFIES
+    for the routing table when every repeat of the split kernel beats every repeat of the fp32 kernel"""
+    from safediffcon_amd.engine import pack_conv_weight, pack_tattn_x3
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    torch.manual_seed(0)
+    wqkv, wo = torch.randn(384, 64, device=DEV) * 0.2, torch.randn(64, 128, device=DEV) * 0.1
+    g = torch.rand(64, device=DEV) + 0.5
+    ang = torch.arange(32, dtype=torch.float32)[:, None] * (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32)))[None, :]
+    rot = torch.stack((ang.cos(), ang.sin()), dim=-1).reshape(-1).to(DEV)
+    bias = torch.randn(4 * 32 * 32, device=DEV) * 0.3
+    wq4, wo4, wpk = pack_conv_weight(wqkv.view(384, 64, 1)), pack_conv_weight(wo.view(64, 128, 1)), pack_tattn_x3(wqkv, wo)
+    for B, hw in ((64, 64), (2, 64), (64, 32), (64, 16)):
+        x = torch.randn(B, 64, 32, hw, hw, device=DEV) * 0.5
+        y4, ys = torch.empty_like(x), torch.empty_like(x)
+        tail = (B, hw * hw, 64, 32, 64 * 32 * hw * hw, 32 * hw * hw, hw * hw, 1e-5)
+        a4 = (x.data_ptr(), g.data_ptr(), wq4.data_ptr(), wo4.data_ptr(), rot.data_ptr(), bias.data_ptr(), y4.data_ptr(), *tail)
+        as_ = (x.data_ptr(), g.data_ptr(), wpk.data_ptr(), rot.data_ptr(), bias.data_ptr(), ys.data_ptr(), *tail)
+        m4, ms = [], []
+        for _ in range(3):          # interleaved repeats of the median of 20: their spread is what a gain has to beat
+            m4.append(_time_call(lib.sdc_tattn_block, a4, stream))
+            ms.append(_time_call(lib.sdc_tattn_block_x3, as_, stream))
+        br = (y4[:1] - x[:1]).double()
+        err = ((ys[:1] - x[:1]).double() - br).pow(2).mean().sqrt().item() / br.pow(2).mean().sqrt().item()
+        med4, meds = statistics.median(m4), statistics.median(ms)
+        routed = bool(lib.sdc_tattn_block_x3_ok(64, 32, hw * hw))
+        print(f"[measured] tattn block B {B} 64 ch 32 frames {hw}x{hw} (inner {hw * hw}, {'routed' if routed else 'not routed'}): "
+              f"ta_block_kernel {' / '.join(f'{v * 1e3:.1f}' for v in m4)} us | ta_block_x3_kernel "
+              f"{' / '.join(f'{v * 1e3:.1f}' for v in ms)} us -> x{med4 / meds:.2f} "
+              f"{'QUALIFIES (every repeat beats every repeat)' if max(ms) < min(m4) else 'does NOT qualify'}; "
+              f"rms difference of the attention branch on sample 0: {err:.2e}", flush=True)
+        del x, y4, ys
+        torch.cuda.empty_cache()
+
+
 def drift(T, stem=False, attn=False):
     torch.manual_seed(0)
     net = sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7).to(DEV)
@@ -443,11 +488,16 @@ if __name__ == "__main__":
     ap.add_argument("--gemm", action="store_true", help="net.gemm_split: the covered convs, launch by launch, and the C4 step with the switch off / on")
     ap.add_argument("--wino", action="store_true", help="net.wino_split: the covered 3x3x3 convs, launch by launch, and the C4 step with the switch off / on")
     ap.add_argument("--attn", action="store_true", help="net.attn_f16: the block launch and the C4 step (with --drift: 4 + attn_f16 against 4)")
-    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --wino / --attn: the per-shape part only")
+    ap.add_argument("--attn-split", action="store_true", help="net.attn_split: the block launch at the sites of the dim-64 smoke net and the C4 step with the switch off / on")
+    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --wino / --attn / --attn-split: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
         drift(a.drift, a.stem, a.attn)
+    elif a.attn_split:
+        attn_split_shapes()
+        if not a.no_step:
+            step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=["4-noasplit", "4+asplit"])
     elif a.attn:
         attn_shapes()
         if not a.no_step:

@@ -118,6 +118,17 @@ def classify(lib, fn, a):
         mm = toks * (2.0 * Cc * 384 + 4 * 2 * 2 * ntok * 32 + 2.0 * 128 * Cc)
         return dict(stage=f"fused temporal-attention block, width {Cc} (norm+qkv+rotary/bias attention+out+res)", kernel="ta_block_kernel",
                     flops=mm + toks * 8.0 * Cc, issued=mm, bytes=8.0 * toks * Cc)
+    if fn is lib.sdc_tattn_block_x3:
+        # (x, g, wpk, rot, bias, y, outer, inner, C, ntok, ...): the FLOP of the block it stands for; only the score and O = V P products
+        # are fp32-MFMA issue -- the projections and the out-projection run as six bf16 MFMAs per product on the other pipe (3x their
+        # FLOP as bf16 issue)
+        outer, inner, Cc, ntok = a[6], a[7], a[8], a[9]
+        toks = outer * inner * ntok
+        core = toks * (4 * 2 * 2 * ntok * 32)
+        mm = toks * (2.0 * Cc * 384 + 2.0 * 128 * Cc) + core
+        return dict(stage=f"fused temporal-attention block, width {Cc} (norm+qkv+rotary/bias attention+out+res) [bf16 split: exact 3-way "
+                          f"operand splits of the weight products on the bf16 matrix pipe]", kernel="ta_block_x3_kernel",
+                    flops=mm + toks * 8.0 * Cc, issued=core, bytes=8.0 * toks * Cc)
     if fn is lib.sdc_attn:
         outer, inner, heads, nt = a[4], a[5], a[6], a[7]
         seqs = outer * inner * heads

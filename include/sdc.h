@@ -228,6 +228,47 @@ int sdc_linattn_block_gn(const float* x_raw, const float* gn_stats, const float*
                          const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
                          int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream);
 
+/* The same block with fp16 operands and fp32 accumulation (net.linattn_f16, opt-in, samplers only; DESIGN.md section 20;
+ * csrc/sdc_lablock_f16.hip).  A switch of its own: sdc_linattn_block, sdc_linattn_block_gn and their buffers are untouched.  The same
+ * three launches, shape domain, strides, token splits and GroupNorm-on-load form.  Rounded once to fp16 (nearest even) as operands of
+ * v_mfma_f32_32x32x16_f16, and nothing else: xn, Wq and Wk (at pack time), the un-normalised probabilities p of the softmax over
+ * tokens, T = Wo ctx (per sequence), q after its softmax and scale.  fp32: both channel norms, the GroupNorm-on-load arithmetic and
+ * the stored h, maxima, exponents, row sums, the split merge, ctx (on the fp32 packed wqkv and wo), every accumulator, the residual
+ * add.  p = exp2(k log2e - ceil(m log2e)) with m the running maximum: every rescale factor is an exact power of two, so the rounding
+ * of p depends neither on the tile order nor on the split count.  An operand beyond 65504 (T has no bound) becomes infinite.
+ *
+ * Weight buffer (sdc_pack_linattn_f16_bytes(C) = 512 C bytes, 16-byte aligned; 0 for another C), from the unpacked 1x1 weight to_qkv
+ * Wqkv (384, C) -- rows mat * 128 + head * 32 + d, mat = 0 q, 1 k.  Every operand fetch of a lane (l31 = lane & 31, lh = lane >> 5) is
+ * one contiguous 16-byte read of 8 fp16 values j = 0 .. 7:
+ *   Wh[mat][head][s][lane][j]       = Wqkv[mat * 128 + head * 32 + l31][16 s + 8 lh + j]       mat < 2, head < 4, s < C / 16
+ * (256 C values: the q fragments of the four heads, then the k fragments).  to_out Wo (C, 128) is part of the call for symmetry with
+ * sdc_pack_tattn_f16 and must not be null, but is not read: T is formed in fp32 from the fp32 packed wo and rounded per sequence.
+ * sdc_pack_linattn_f16 writes the buffer on the device, one launch on `stream` (SDC_ENULL for a null pointer, SDC_EINVAL for another
+ * C, SDC_EALIGN for a misaligned dst).
+ *
+ * Scratch (sdc_linattn_block_f16_bytes, 16-byte aligned): the fp32 partials of sdc_linattn_block, then per sequence the fp16 K fragments
+ *   Tf[rt][s][lane][j]              = T[32 rt + l31][32 (s >> 1) + row(8 (s & 1) + j, lh)]      rt < C / 32, s < 8
+ * with row(r, lh) = (r & 3) + 8 (r >> 2) + 4 lh, the accumulator row that register r of a 32x32 MFMA result holds on half-wave lh: the
+ * kernel's q operand arrives in that order.
+ *
+ * sdc_linattn_block_f16 / sdc_linattn_block_gn_f16: arguments, strides and checks of sdc_linattn_block / sdc_linattn_block_gn with wpk
+ * behind (wqkv, wo), which stay the fp32 packed [C][384] / [128][C] weights.  SDC_ENULL for a null pointer, SDC_EINVAL for a bad shape or
+ * mode, SDC_EALIGN for a wpk or work that is not 16-byte aligned, all before any launch.  No atomics, fixed accumulation order; a
+ * sample's output does not depend on the batch.
+ * sdc_linattn_block_f16_ok: 1 where net.linattn_f16 routes a fused site of width C and n tokens per sequence (never the batch) to
+ * these entries: every covered (C, n). */
+size_t sdc_pack_linattn_f16_bytes(int C);
+int sdc_pack_linattn_f16(const float* wqkv, const float* wo, int C, void* dst, void* stream);
+size_t sdc_linattn_block_f16_bytes(int outer, int inner, int C, int64_t n);
+int sdc_linattn_block_f16(const float* x, const float* g_pre, const float* wqkv, const float* wo, const void* wpk, const float* bo,
+                          const float* g_post, void* work, float* y, int outer, int inner, int C, int64_t n,
+                          int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream);
+int sdc_linattn_block_gn_f16(const float* x_raw, const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_G,
+                             const float* gn_residual, const float* g_pre, const float* wqkv, const float* wo, const void* wpk,
+                             const float* bo, const float* g_post, void* work, float* y, int outer, int inner, int C, int64_t n,
+                             int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream);
+int sdc_linattn_block_f16_ok(int C, int64_t n);
+
 /* Fused temporal-attention block of the smoke U-Net, dim 64, 32 frames, heads 4 x 32:
  *   y = x + Wo . softmax( rot(s Wq xn) rot(Wk xn)^T + relpos ) (Wv xn),  xn = channel LayerNorm(x) * gamma
  * Residual(PreNorm(dim, EinopsToAndFrom(Attention))): conv3d.py:165-184,262-275,277-353,383,402-405.

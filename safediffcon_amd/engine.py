@@ -179,6 +179,21 @@ def pack_tattn_f16(wqkv, wo):
     return torch.cat([a.reshape(-1), b.reshape(-1)]).half().view(torch.float32)
 
 
+def pack_linattn_f16(wqkv, wo):
+    """fp16 buffer of the LinearAttention weights for sdc_linattn_block_f16 / sdc_linattn_block_gn_f16 (include/sdc.h; host twin of
+    sdc_pack_linattn_f16, bit for bit) from the unpacked 1x1 weights to_qkv (384, C) and to_out (C, 128), C in {64, 128} (trailing
+    unit axes of a conv weight are dropped), rounded to fp16 (RNE): every operand fetch of a lane (l31 = lane & 31, lh = lane >> 5) is
+    8 contiguous values j -- Wh[mat][head][s][lane][j] = Wqkv[mat * 128 + head * 32 + l31][16 s + 8 lh + j], mat = 0 q, 1 k, s < C / 16.
+    to_out is checked and not read (T = Wo ctx is formed in fp32 and rounded per sequence); returned as the float32 words that hold it"""
+    wqkv, wo = wqkv.to(torch.float32), wo.to(torch.float32)
+    wqkv, wo = wqkv.reshape(wqkv.shape[0], -1), wo.reshape(wo.shape[0], -1)
+    Cc = wqkv.shape[1]
+    if Cc not in (64, 128) or tuple(wqkv.shape) != (384, Cc) or tuple(wo.shape) != (Cc, 128):
+        raise ValueError(f"pack_linattn_f16: to_qkv (384, C) and to_out (C, 128), C 64 or 128 (got {tuple(wqkv.shape)}, {tuple(wo.shape)})")
+    a = wqkv[:256].reshape(2, 4, 32, Cc // 16, 2, 8).permute(0, 1, 3, 4, 2, 5)         # [mat][head][d][s][lh][j] -> [mat][head][s][lh][d][j]
+    return a.reshape(-1).half().view(torch.float32)
+
+
 def pack_tattn_x3(wqkv, wo):
     """bf16 buffer of the temporal-attention weights for sdc_tattn_block_x3 (include/sdc.h; host twin of sdc_pack_tattn_x3, bit for bit)
     from the nn.Linear weights to_qkv (384, 64) and to_out (64, 128): Wb[head][piece][e], e < 8192 -- position e of a head in
@@ -296,7 +311,7 @@ class Plan:
     """Recorded kernel calls; `run(stream)` replays them (the samplers capture that replay into a hipGraph)."""
 
     def __init__(self, device, precision=0, stem_f16=False, stem_split=False, gemm_split=False, attn_f16=False, wino_split=False,
-                 attn_split=False):
+                 attn_split=False, linattn_f16=False):
         self.device = torch.device(device)
         self.lib = _lib.get_lib()
         # conv algorithm (include/sdc.h): 0 direct fp32 MFMA | 2 fp32 Winograd F(2,3) along W | 3 F(2x2,3x3) over (H, W) where
@@ -334,6 +349,10 @@ class Plan:
         # (csrc/sdc_tablock_x3.hip: the weight products with the stem_split arithmetic, the rest with the fp32 block's instructions) on
         # their pack_tattn_x3 buffer.  Every other precision keeps today's calls; attn_f16 wins
         self.attn_split = bool(attn_split) and self.precision in (4, 5) and not self.attn_f16
+        # net.linattn_f16 (opt-in, samplers only, at any precision): the fused LinearAttention block (Plan.linattn_block) runs the
+        # la16_* kernels (fp16 operands, fp32 accumulation; csrc/sdc_lablock_f16.hip) on a buffer of its own (pack_linattn_f16) where
+        # sdc_linattn_block_f16_ok lists the site; everything else, and every call with the switch off, is recorded exactly as without it
+        self.linattn_f16 = bool(linattn_f16)
         self.calls = []          # (fn, args, keepalive)
         self.pool = Pool(self.device)
         self.keep = []           # descriptors / tensors that must outlive the plan
@@ -609,12 +628,36 @@ class Plan:
                    B, Cc, groups, cout, S, plane, ys[0], ys[1], ys[2])
         return out
 
-    def linattn_block(self, x, g_pre, wqkv, wo, bo, g_post, outer, inner, n, strides, pre_mode, post_mode, eps=1e-5, gn=None):
+    def linattn_f16_routes(self, Cc, n):
+        """True where net.linattn_f16 sends a fused LinearAttention site of width Cc and n tokens per sequence to
+        sdc_linattn_block_f16 / _gn_f16: the switch is on and the library lists the site (never the batch)"""
+        return self.linattn_f16 and bool(self.lib.sdc_linattn_block_f16_ok(int(Cc), int(n)))
+
+    def linattn_block(self, x, g_pre, wqkv, wo, bo, g_post, outer, inner, n, strides, pre_mode, post_mode, eps=1e-5, gn=None, w16=None):
         """Residual(PreNorm(LinearAttention)) in one call (dim 64 / 128, n % 64 == 0); returns y shaped like x.
         gn = (stats, gamma, beta, groups, residual): x is the RAW conv output of the producing ResnetBlock, whose GroupNorm +
-        SiLU + residual add is applied on load (sdc_linattn_block_gn); `outer` must then be the batch axis."""
+        SiLU + residual add is applied on load (sdc_linattn_block_gn); `outer` must then be the batch axis.
+        w16 = the UNPACKED weights (to_qkv (384, C), to_out (C, 128)) or callables returning them: where linattn_f16_routes() lists
+        the site the call recorded is sdc_linattn_block_f16 / sdc_linattn_block_gn_f16 on their pack_linattn_f16 buffer (wqkv and wo,
+        the fp32 packed weights, still serve its fp32 middle launch)."""
         Cc = x.shape[1]
         y = self.pool.get(tuple(x.shape))
+        if w16 is not None and self.linattn_f16_routes(Cc, n):
+            uq, uo = w16
+            wpk = self.packed(lambda: pack_linattn_f16(uq() if callable(uq) else uq, uo() if callable(uo) else uo))
+            work = torch.empty((int(self.lib.sdc_linattn_block_f16_bytes(outer, inner, Cc, n)) + 3) // 4, dtype=torch.float32, device=self.device)
+            self.keep += [x, g_pre, wqkv, wo, wpk, bo, g_post, work, y]
+            if gn is not None:
+                st, gamma, beta, groups, res = gn
+                assert outer == x.shape[0] and (res is None or (tuple(res.shape) == tuple(x.shape) and res.stride() == x.stride()))
+                self.keep += [st, gamma, beta, res]
+                self._emit(self.lib.sdc_linattn_block_gn_f16, _ptr(x), _ptr(st), _ptr(gamma), _ptr(beta), groups, _ptr(res), _ptr(g_pre),
+                           _ptr(wqkv), _ptr(wo), _ptr(wpk), _ptr(bo), _ptr(g_post), _ptr(work), _ptr(y), outer, inner, Cc, n, *strides,
+                           pre_mode, post_mode, eps)
+                return y
+            self._emit(self.lib.sdc_linattn_block_f16, _ptr(x), _ptr(g_pre), _ptr(wqkv), _ptr(wo), _ptr(wpk), _ptr(bo), _ptr(g_post),
+                       _ptr(work), _ptr(y), outer, inner, Cc, n, *strides, pre_mode, post_mode, eps)
+            return y
         work = torch.empty(int(self.lib.sdc_linattn_block_bytes(outer, inner, Cc, n)) // 4, dtype=torch.float32, device=self.device)
         self.keep += [x, g_pre, wqkv, wo, bo, g_post, work, y]
         if gn is not None:

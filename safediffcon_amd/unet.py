@@ -334,6 +334,13 @@ class _HipUNet(nn.Module):
         # wider layers, the unfused chain (fuse_linattn = False), forward_train, GraphedLossStep and the differentiable DDIM step
         # ignore it.
         self.attn_f16 = False
+        # the fused LinearAttention blocks of the sampler plans (width 64 / 128, n % 64 == 0: the sites that take the fused fp32 block
+        # today) on the fp16 matrix pipe (opt-in): xn, Wq, Wk, the un-normalised probabilities of the softmax over tokens, T = Wo ctx
+        # and q after its softmax rounded to nearest even as operands, fp32 accumulation; the channel norms, GroupNorm-on-load, the
+        # softmax statistics, the split merge, ctx and the residual stay fp32 (csrc/sdc_lablock_f16.hip).  Works at any `precision`;
+        # read when a plan is built (plans are cached per value).  Wider layers, the unfused chain (fuse_linattn = False),
+        # forward_train, GraphedLossStep and the differentiable DDIM step ignore it.
+        self.linattn_f16 = False
         # the same stem conv of the sampler plans at precision >= 4 (default on): fp32 products formed on the bf16 matrix pipe from
         # exact three-way operand splits (x = bf16 h + m + l, six MFMAs per product, fp32 accumulation; conv_stem_x3_kernel) where it
         # covers the stem (the coverage of stem_f16).  An fp32-grade result in another rounding order, like the Winograd modes -- not a
@@ -522,7 +529,8 @@ class _HipUNet(nn.Module):
         (lut=False, forward(x, time)) or one row per timestep read through a device-side t (lut=True, samplers)."""
         key = (tuple(shape), rows, bool(lut), int(self.precision), bool(self.fuse_linattn), bool(self.subpixel_upsample),
                bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16),
-               bool(self.stem_split), bool(self.gemm_split), bool(self.attn_f16), bool(self.wino_split), bool(self.attn_split))
+               bool(self.stem_split), bool(self.gemm_split), bool(self.attn_f16), bool(self.wino_split), bool(self.attn_split),
+               bool(self.linattn_f16))
         stamp = self._weights_stamp()
         ent = self._plans.get(key)
         if ent is not None and ent["wstamp"] != stamp:        # parameters changed since this plan packed them
@@ -534,7 +542,7 @@ class _HipUNet(nn.Module):
                                    "there is no CPU fallback")
             plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16), stem_split=bool(self.stem_split),
                         gemm_split=bool(self.gemm_split), attn_f16=bool(self.attn_f16), wino_split=bool(self.wino_split),
-                        attn_split=bool(self.attn_split))
+                        attn_split=bool(self.attn_split), linattn_f16=bool(self.linattn_f16))
             plan.split_small_grids = bool(self.split_small_grids)
             x = torch.zeros(shape, dtype=torch.float32, device=dev)
             eps = torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -650,7 +658,8 @@ class _LucidUNet(_HipUNet):
         if self.fuse_linattn and C in (64, 128) and n % 64 == 0:
             return plan.linattn_block(x, b.V(f"{prefix}.fn.norm.g"), b.W(f"{prefix}.fn.fn.to_qkv.weight"),
                                       b.W(f"{prefix}.fn.fn.to_out.0.weight"), b.V(f"{prefix}.fn.fn.to_out.0.bias"),
-                                      b.V(f"{prefix}.fn.fn.to_out.1.g"), B, 1, n, (C * n, n, 0), self.NORM_MODE, self.NORM_MODE)
+                                      b.V(f"{prefix}.fn.fn.to_out.1.g"), B, 1, n, (C * n, n, 0), self.NORM_MODE, self.NORM_MODE,
+                                      w16=(lambda: self.P(f"{prefix}.fn.fn.to_qkv.weight"), lambda: self.P(f"{prefix}.fn.fn.to_out.0.weight")))
         xn = plan.chan_norm(x, b.V(f"{prefix}.fn.norm.g"), self.NORM_MODE)
         qkv = b.conv(xn, f"{prefix}.fn.fn.to_qkv", bias=False)
         pool.put(xn)
@@ -852,7 +861,8 @@ class Unet3D_with_Conv3D(_HipUNet):
         if self._la_fusable(x.shape):
             return plan.linattn_block(x, b.V(f"{prefix}.fn.norm.gamma"), b.W(f"{prefix}.fn.fn.to_qkv.weight"),
                                       b.W(f"{prefix}.fn.fn.to_out.weight"), b.V(f"{prefix}.fn.fn.to_out.bias"), None,
-                                      B, F, hw, (C * F * hw, F * hw, hw), 0, -1, gn=gn)
+                                      B, F, hw, (C * F * hw, F * hw, hw), 0, -1, gn=gn,
+                                      w16=(lambda: self.P(f"{prefix}.fn.fn.to_qkv.weight"), lambda: self.P(f"{prefix}.fn.fn.to_out.weight")))
         assert gn is None
         xn = plan.chan_norm(x, b.V(f"{prefix}.fn.norm.gamma"), 0)
         qkv = b.conv(xn, f"{prefix}.fn.fn.to_qkv", bias=False)

@@ -36,6 +36,14 @@
       against 4 + attn_f16 and 6 + stem_f16 against 6 + stem_f16 + attn_f16, the four arms interleaved round by round
   python tools/f16_step.py --drift [T] --attn
       the T-step guided smoke trajectories with precision 4 + net.attn_f16 against 4
+  python tools/f16_step.py --linattn [--workloads c4,c2] [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
+      net.linattn_f16 (csrc/sdc_lablock_f16.hip): the fused LinearAttention block at the C4 sites (B = 64: C 64, n 4096, 32 frames, the
+      plain and the GroupNorm-on-load form; C 128, n 1024), the C2 sites (B = 256: C 64, n 2048; C 128, n 512) and at B = 2,
+      sdc_linattn_block / _gn against sdc_linattn_block_f16 / _gn_f16 on the same buffers, the medians of 20 launches in three interleaved
+      repeats (the rule of DESIGN section 15); then the C4 sampler step, precision 4 against 4 + linattn_f16 and 6 + stem_f16 + attn_f16
+      against the same + linattn_f16, the four arms interleaved round by round, and the C2 step, 4 against 4 + linattn_f16
+  python tools/f16_step.py --drift [T] --linattn
+      the T-step guided smoke trajectories with precision 4 + net.linattn_f16 against 4
   python tools/f16_step.py --attn-split [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
       net.attn_split (csrc/sdc_tablock_x3.hip): the fused temporal-attention block at the sites of the dim-64 smoke net -- 64 x 64 pixels
       per sample at B = 64 (the C4 site) and B = 2, 32 x 32 and 16 x 16 at B = 64 --, sdc_tattn_block against sdc_tattn_block_x3 on the same
@@ -64,7 +72,7 @@ DEV = torch.device("cuda:0")
 
 def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
     """arms: the precisions timed, interleaved; a string 'P+stem' is precision P with net.stem_f16, 'P+attn' with net.attn_f16 (both:
-    'P+stem+attn'), 'P-nosplit' precision P with net.stem_split off, 'P-nogemm' precision P with net.gemm_split off, 'P-nowino' / 'P+wino' precision P
+    'P+stem+attn'), 'P+la' with net.linattn_f16, 'P-nosplit' precision P with net.stem_split off, 'P-nogemm' precision P with net.gemm_split off, 'P-nowino' / 'P+wino' precision P
     with net.wino_split off / on, 'P-noasplit' / 'P+asplit' with net.attn_split off / on (default: 4 against `arm`)"""
     torch.cuda.set_device(DEV)
     side = torch.cuda.Stream(device=DEV)
@@ -78,6 +86,7 @@ def step_ab(names, steps, warmup, rounds, arm=6, arms=None):
                 W = bench.workload(name, None, B, DEV, 0, 1, precision=int(tag.split("+")[0].split("-")[0]), cal_steps=0)
                 W["gd"].model.stem_f16 = "+stem" in tag                 # (read when prep() builds the sampler's plan)
                 W["gd"].model.attn_f16 = "+attn" in tag
+                W["gd"].model.linattn_f16 = "+la" in tag
                 W["gd"].model.stem_split = not tag.endswith("-nosplit")
                 W["gd"].model.gemm_split = not tag.endswith("-nogemm")
                 if tag.endswith("-noasplit") or "+asplit" in tag:
@@ -414,6 +423,54 @@ def attn_shapes():
         torch.cuda.empty_cache()
 
 
+def linattn_shapes():
+    """the fused LinearAttention block at the C4 and C2 sites and at B = 2: sdc_linattn_block / _gn against sdc_linattn_block_f16 / _gn_f16
+    on the same buffers; the medians of 20 launches, three interleaved repeats; FASTER when every repeat beats every repeat"""
+    from safediffcon_amd.engine import pack_conv_weight, pack_linattn_f16
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    torch.manual_seed(0)
+    # (outer, inner, C, n, GroupNorm-on-load, norm modes): smoke SpatialLinearAttention (LayerNorm in, none out), Burgers LayerNorm in and out
+    sites = [(64, 32, 64, 4096, True, 0, -1), (64, 32, 64, 4096, False, 0, -1), (64, 32, 128, 1024, True, 0, -1),
+             (256, 1, 64, 2048, False, 0, 0), (256, 1, 128, 512, False, 0, 0),
+             (2, 32, 64, 4096, True, 0, -1), (2, 32, 128, 1024, True, 0, -1), (2, 1, 64, 2048, False, 0, 0), (2, 1, 128, 512, False, 0, 0)]
+    for outer, inner, Cc, n, gn, pre, post in sites:
+        wqkv, wo = torch.randn(384, Cc, device=DEV) * 0.2, torch.randn(Cc, 128, device=DEV) * 0.1
+        g1, g2, bo = torch.rand(Cc, device=DEV) + 0.5, torch.rand(Cc, device=DEV) + 0.5, torch.randn(Cc, device=DEV) * 0.1
+        wq4, wo4, wpk = pack_conv_weight(wqkv.view(384, Cc, 1)), pack_conv_weight(wo.view(Cc, 128, 1)), pack_linattn_f16(wqkv, wo).to(DEV)
+        x = torch.randn(outer, Cc, inner, n, device=DEV) * 0.5
+        y4, yh = torch.empty_like(x), torch.empty_like(x)
+        w4 = torch.empty(int(lib.sdc_linattn_block_bytes(outer, inner, Cc, n)) // 4, device=DEV)
+        wh = torch.empty((int(lib.sdc_linattn_block_f16_bytes(outer, inner, Cc, n)) + 3) // 4, device=DEV)
+        tail = (outer, inner, Cc, n, Cc * inner * n, inner * n, n, pre, post, 1e-5)
+        gp = g2.data_ptr() if post >= 0 else None
+        head = (x.data_ptr(),)
+        if gn:
+            st = torch.stack((torch.randn(outer * 8, device=DEV) * 0.1, torch.rand(outer * 8, device=DEV) + 0.5), -1).reshape(-1).contiguous()
+            gam, bet, res = torch.rand(Cc, device=DEV) + 0.5, torch.randn(Cc, device=DEV) * 0.1, torch.randn_like(x) * 0.5
+            head = (x.data_ptr(), st.data_ptr(), gam.data_ptr(), bet.data_ptr(), 8, res.data_ptr())
+        a4 = (*head, g1.data_ptr(), wq4.data_ptr(), wo4.data_ptr(), bo.data_ptr(), gp, w4.data_ptr(), y4.data_ptr(), *tail)
+        ah = (*head, g1.data_ptr(), wq4.data_ptr(), wo4.data_ptr(), wpk.data_ptr(), bo.data_ptr(), gp, wh.data_ptr(), yh.data_ptr(), *tail)
+        f4, fh = ((lib.sdc_linattn_block_gn, lib.sdc_linattn_block_gn_f16) if gn else (lib.sdc_linattn_block, lib.sdc_linattn_block_f16))
+        m4, mh = [], []
+        for _ in range(3):          # interleaved repeats of the median of 20: their spread is what a gain has to beat
+            m4.append(_time_call(f4, a4, stream))
+            mh.append(_time_call(fh, ah, stream))
+        # the branch y - h on sequence block 0 (the plain form: h = x)
+        br = y4[:1].double()
+        err = (yh[:1].double() - br).pow(2).mean().sqrt().item() / (br - (0 if gn else x[:1].double())).pow(2).mean().sqrt().item()
+        med4, medh = statistics.median(m4), statistics.median(mh)
+        # tensor passes over HBM: x read by pass 1 and by pass 2, y written; GroupNorm-on-load: raw x and the residual read, h written,
+        # h read back, y written
+        gb = (5.0 if gn else 3.0) * x.numel() * 4 / 1e9
+        print(f"[measured] linattn block {'gn ' if gn else ''}outer {outer} inner {inner} C {Cc} n {n}: la_blk {' / '.join(f'{v * 1e3:.1f}' for v in m4)} us"
+              f" | la16 {' / '.join(f'{v * 1e3:.1f}' for v in mh)} us ({gb / medh:.2f} TB/s of its HBM traffic) -> x{med4 / medh:.2f} "
+              f"{'FASTER (every repeat beats every repeat)' if max(mh) < min(m4) else 'NOT faster by the rule'}; "
+              f"rms difference on sample 0 of y{'' if gn else ', of the attention branch'}: {err:.2e}", flush=True)
+        del x, y4, yh, w4, wh
+        torch.cuda.empty_cache()
+
+
 def attn_split_shapes():
     """net.attn_split: sdc_tattn_block against sdc_tattn_block_x3 on the same buffers at the sites of the dim-64 smoke net -- 64 x 64 (the
     C4 site, B = 64 and B = 2), 32 x 32 and 16 x 16 (B = 64); the medians of 20 launches, three interleaved repeats; a shape QUALIFIES
@@ -451,17 +508,18 @@ def attn_split_shapes():
         torch.cuda.empty_cache()
 
 
-def drift(T, stem=False, attn=False):
+def drift(T, stem=False, attn=False, linattn=False):
     torch.manual_seed(0)
     net = sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7).to(DEV)
     init = (torch.rand(2, 64, 64) * 0.2).to(DEV)
     control = (torch.randn(2, 32, 2, 64, 64) * 0.3).to(DEV)
     outs = {}
-    arms = (4, "4+attn") if attn else (4, "4+stem", "6+stem") if stem else (4, 6, 7)
+    arms = (4, "4+la") if linattn else (4, "4+attn") if attn else (4, "4+stem", "6+stem") if stem else (4, 6, 7)
     for prec in arms:
         net.precision = int(prec.split("+")[0]) if isinstance(prec, str) else prec
         net.stem_f16 = "+stem" in str(prec)
         net.attn_f16 = "+attn" in str(prec)
+        net.linattn_f16 = "+la" in str(prec)
         gs = sdc.GaussianDiffusionSmoke(net, image_size=64, frames=32, timesteps=T, standard_fixed_ratio=100.0).to(DEV)
         torch.manual_seed(7)
         t0 = time.perf_counter()
@@ -488,12 +546,20 @@ if __name__ == "__main__":
     ap.add_argument("--gemm", action="store_true", help="net.gemm_split: the covered convs, launch by launch, and the C4 step with the switch off / on")
     ap.add_argument("--wino", action="store_true", help="net.wino_split: the covered 3x3x3 convs, launch by launch, and the C4 step with the switch off / on")
     ap.add_argument("--attn", action="store_true", help="net.attn_f16: the block launch and the C4 step (with --drift: 4 + attn_f16 against 4)")
+    ap.add_argument("--linattn", action="store_true", help="net.linattn_f16: the block launch at the C4 / C2 sites, the C4 and C2 steps (with --drift: 4 + linattn_f16 against 4)")
     ap.add_argument("--attn-split", action="store_true", help="net.attn_split: the block launch at the sites of the dim-64 smoke net and the C4 step with the switch off / on")
     ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --wino / --attn / --attn-split: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
-        drift(a.drift, a.stem, a.attn)
+        drift(a.drift, a.stem, a.attn, a.linattn)
+    elif a.linattn:
+        linattn_shapes()
+        if not a.no_step:
+            if "c4" in wls:
+                step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=[4, "4+la", "6+stem+attn", "6+stem+attn+la"])
+            if "c2" in wls:
+                step_ab(["c2"], a.steps, a.warmup, a.rounds, arms=[4, "4+la"])
     elif a.attn_split:
         attn_split_shapes()
         if not a.no_step:

@@ -6,6 +6,7 @@ plan from a reuse pool, handed to the kernels as raw pointers, and the recorded
 call list is either replayed from Python or captured into one hipGraph.
 Nothing in this file computes on the CPU or through torch ops on the hot path.
 """
+import collections
 import ctypes as C
 import functools
 import os
@@ -19,6 +20,11 @@ from ._lib import SdcConvDesc, check
 
 def _ptr(t):
     return 0 if t is None else t.data_ptr()
+
+
+def _val(x):
+    """x, or x() where a weight is handed over as a callable that reads the live parameter"""
+    return x() if callable(x) else x
 
 
 def _s5(t):
@@ -284,6 +290,46 @@ def conv_desc(x, x1, out, residual, cout, k, stride, pad, up, up_mode, precision
     return d
 
 
+# The switches of a sampler plan that send calls to an alternate kernel: keyword arguments of Plan (documented there), attributes of
+# the nets with the same names (unet.py), part of the nets' plan cache key in this order.
+PLAN_SWITCHES = ("stem_f16", "stem_split", "gemm_split", "attn_f16", "wino_split", "attn_split", "linattn_f16")
+
+# An unpacked conv weight for Plan.conv: w = the nn weight tensor or a callable returning it, kind as for pack_conv_weight.
+WeightSrc = collections.namedtuple("WeightSrc", "w kind", defaults=("conv",))
+
+ConvRoute = collections.namedtuple("ConvRoute", "switch ok fn taps precision x1 gn splitk pack")
+# The alternate conv kernels of Plan.conv, in priority order.  A conv with a residual never takes one.  To add a route: one entry here,
+# one name in PLAN_SWITCHES (with its Plan keyword and net attribute), the prototypes of its entry points in _lib.py.
+#   switch     Plan attribute that enables it, after the constructor's gating
+#   ok, fn     coverage query and launch entry points of the library
+#   taps       kind -> tap pre-filter; a kind not named never takes the route
+#   precision  SdcConvDesc.precision of its descriptor
+#   x1         takes a second, channel-concatenated input (its entry point then has the x1 argument)
+#   gn         with gn_groups: "ignore" routes and registers no partial sums | "decline" does not route | "sums" routes and registers
+#              its epilogue sums like sdc_conv_gn (its entry point then has the partial-sum and group-count arguments)
+#   splitk     yields to sdc_conv_splitk under split_small_grids
+#   pack       its buffer from the unpacked weight
+CONV_ROUTES = (
+    # the 7-tap stem convs: the stem kernels sum no GroupNorm statistics (gn_silu takes its own pass) and do not split K
+    ConvRoute(switch="stem_f16", ok="sdc_conv_stem_f16_ok", fn="sdc_conv_stem_f16", taps={"conv": lambda k: k[2] == 7}, precision=0,
+              x1=False, gn="ignore", splitk=False, pack=lambda w, kind, cout, cin, k: pack_stem_f16(w)),
+    ConvRoute(switch="stem_split", ok="sdc_conv_stem_x3_ok", fn="sdc_conv_stem_x3", taps={"conv": lambda k: k[2] == 7}, precision=0,
+              x1=False, gn="ignore", splitk=False, pack=lambda w, kind, cout, cin, k: pack_stem_x3(w)),
+    # the strided (1,4,4) and 1x1x1 convs and the sub-pixel parities of conv_transpose_422; never "unshuffle", "convT" or "up2_sub", whose
+    # 2x2 / merged-tap descriptors the coverage query alone would not keep out.  A conv whose GroupNorm sums the fp32 epilogue can
+    # carry keeps the fp32 kernels
+    ConvRoute(switch="gemm_split", ok="sdc_conv_gemm_x3_ok", fn="sdc_conv_gemm_x3",
+              taps={"conv": lambda k: k in ((1, 4, 4), (1, 1, 1)), "convT_sub": lambda k: k == (1, 2, 2)}, precision=0,
+              x1=False, gn="decline", splitk=True,
+              pack=lambda w, kind, cout, cin, k: pack_gemm_x3(pack_conv_weight(w, kind, 0), cout, cin, k)),
+    # the 3x3x3 convs in precision 4's F(2x2x2,3x3x3) form, GroupNorm sums in the epilogue included
+    ConvRoute(switch="wino_split", ok="sdc_conv_wino3_x3_ok", fn="sdc_conv_wino3_x3", taps={"conv": lambda k: k == (3, 3, 3)}, precision=4,
+              x1=True, gn="sums", splitk=True,
+              pack=lambda w, kind, cout, cin, k: pack_wino3_x3(pack_conv_weight(w, "conv", 4), cout, cin)),
+)
+assert all(r.switch in PLAN_SWITCHES for r in CONV_ROUTES)
+
+
 class Pool:
     """Size-keyed free list so that activation buffers are reused along the plan."""
 
@@ -405,30 +451,35 @@ class Plan:
 
     def conv_weight(self, w, kind="conv"):
         """Register the kernel layout of a conv weight (pack_conv_weight), refreshed by refresh_weights()."""
-        return self.packed(lambda: pack_conv_weight(w() if callable(w) else w, kind, self.precision))
+        return self.packed(lambda: pack_conv_weight(_val(w), kind, self.precision))
 
     def stem_weight(self, w, pack=pack_stem_f16):
         """Register the 16-bit buffer of a covered stem conv weight (pack_stem_f16 / pack_stem_x3), refreshed by refresh_weights()."""
-        return self.packed(lambda: pack(w() if callable(w) else w))
+        return self.packed(lambda: pack(_val(w)))
 
     def vec(self, p):
-        return self.packed(lambda: (p() if callable(p) else p).reshape(-1))
+        return self.packed(lambda: _val(p).reshape(-1))
 
     # ------------------------------------------------------------------ stages
-    def conv(self, x, wp, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), up_mode=0,
-             residual=None, out=None, gn_groups=0, stem_w=None, gemm_w=None, wino_w=None):
+    def _gn_partials(self, d, out, gn_groups):
+        """Partial-sum buffer for a conv whose epilogue sums the statistics of the GroupNorm over `out` that follows (sdc_conv_gn,
+        sdc_conv_wino3_x3), registered for the gn_silu call on `out`; None where the kernel of descriptor d cannot sum them."""
+        nparts = int(self.lib.sdc_conv_gnparts(C.byref(d), gn_groups)) if (gn_groups and self.fuse_gn_stats) else 0
+        if nparts <= 0:
+            return None
+        parts = torch.empty(d.B * gn_groups * nparts * 2, dtype=torch.float64, device=self.device)
+        self.keep.append(parts)
+        self._gn_parts[out.data_ptr()] = (parts, nparts, gn_groups)
+        return parts
+
+    def conv(self, x, w, bias, cout, k, *, x1=None, stride=(1, 1, 1), pad=(0, 0, 0), up=(1, 1, 1), up_mode=0,
+             residual=None, out=None, gn_groups=0):
         """x (and optional x1, channel-concatenated) are 5-D views; returns out (B,cout,oD,oH,oW).
-        gn_groups > 0: a GroupNorm over `out` follows -- where the conv epilogue can sum its statistics (sdc_conv_gn) the
-        partial sums are kept for the gn_silu call on `out`, which then skips its own pass over the tensor.
-        stem_w: the unpacked weight (or a callable returning it) of a conv that may be a 7-tap stem: with Plan.stem_f16, where
-        sdc_conv_stem_f16_ok covers the descriptor, the call recorded is sdc_conv_stem_f16 on its pack_stem_f16 buffer; with
-        Plan.stem_split, where sdc_conv_stem_x3_ok does, sdc_conv_stem_x3 on its pack_stem_x3 buffer; wp may then be a callable,
-        packed only when the conv takes the usual path.
-        gemm_w: a callable returning the conv's Wp [taps * Cin][Cout] (pack_conv_weight at precision 0): with Plan.gemm_split, where
-        sdc_conv_gemm_x3_ok lists the descriptor, the call recorded is sdc_conv_gemm_x3 on its pack_gemm_x3 buffer (wp as for stem_w).
-        wino_w: a callable returning the conv's precision-4 buffer (pack_conv_weight at precision 4): with Plan.wino_split, where
-        sdc_conv_wino3_x3_ok lists the descriptor, the call recorded is sdc_conv_wino3_x3 on its pack_wino3_x3 buffer (wp as for stem_w);
-        with gn_groups its epilogue sums are registered for the gn_silu call on `out` exactly as sdc_conv_gn's are."""
+        w: the conv's packed buffer (conv_weight), or a WeightSrc -- the unpacked weight and its kind.  Only a WeightSrc can take one of
+        CONV_ROUTES: the first route whose switch is on and whose fields and `_ok` entry point accept the conv records its kernel on
+        its own buffer, and the fp32 buffer (pack_conv_weight at the plan's precision) is packed only when no route takes the conv.
+        gn_groups > 0: a GroupNorm over `out` follows -- where the conv epilogue can sum its statistics (sdc_conv_gn, sdc_conv_wino3_x3)
+        the partial sums are kept for the gn_silu call on `out`, which then skips its own pass over the tensor."""
         B, c0, iD, iH, iW = x.shape
         c1 = 0 if x1 is None else x1.shape[1]
 
@@ -444,48 +495,29 @@ class Plan:
             # library validates it
             assert tuple(out.shape[:2]) == (B, cout) and out.dim() == 5, (out.shape, (B, cout, *o))
             o = tuple(out.shape[2:])
-        if (self.stem_f16 or self.stem_split) and stem_w is not None and x1 is None and residual is None:
-            d = conv_desc(x, None, out, None, cout, k, stride, pad, up, up_mode, 0)
-            ok, fn, pack = ((self.lib.sdc_conv_stem_f16_ok, self.lib.sdc_conv_stem_f16, pack_stem_f16) if self.stem_f16 else
-                            (self.lib.sdc_conv_stem_x3_ok, self.lib.sdc_conv_stem_x3, pack_stem_x3))
-            if ok(C.byref(d)):
-                # (gn_groups and split_small_grids are not looked at: the stem kernels neither sum GroupNorm statistics nor split K;
-                # a gn_silu on `out` finds no partial sums registered and takes its own statistics pass)
-                wh = self.stem_weight(stem_w, pack)
-                self.keep += [d, x, wh, bias, out]
-                self._emit(fn, C.byref(d), _ptr(x), _ptr(wh), _ptr(bias), _ptr(out))
-                return out
-        if self.gemm_split and gemm_w is not None and x1 is None and residual is None and not gn_groups:
-            # (a conv whose GroupNorm sums the fp32 epilogue could carry, one with a residual or a second input, and one that
-            # sdc_conv_splitk would take, keep the usual path: conv_gemm_x3_kernel has none of these forms)
-            d = conv_desc(x, None, out, None, cout, k, stride, pad, up, up_mode, 0)
-            if self.lib.sdc_conv_gemm_x3_ok(C.byref(d)) and not (self.split_small_grids and self.lib.sdc_conv_splitk_bytes(C.byref(d))):
-                wb = self.packed(lambda: pack_gemm_x3(gemm_w(), cout, c0, k))
-                self.keep += [d, x, wb, bias, out]
-                self._emit(self.lib.sdc_conv_gemm_x3, C.byref(d), _ptr(x), _ptr(wb), _ptr(bias), _ptr(out))
-                return out
-        if self.wino_split and wino_w is not None and residual is None:
-            # (a conv with a residual, and one that sdc_conv_splitk would take, keep the usual path: conv_wg3_x3_kernel has neither form)
-            d = conv_desc(x, x1, out, None, cout, k, stride, pad, up, up_mode, 4)
-            if self.lib.sdc_conv_wino3_x3_ok(C.byref(d)) and not (self.split_small_grids and self.lib.sdc_conv_splitk_bytes(C.byref(d))):
-                wb = self.packed(lambda: pack_wino3_x3(wino_w(), cout, c0 + c1))
+        if isinstance(w, WeightSrc):
+            src = w
+            kname = src.kind[0] if isinstance(src.kind, tuple) else src.kind
+            for r in CONV_ROUTES:
+                if not (getattr(self, r.switch) and residual is None and (x1 is None or r.x1) and not (gn_groups and r.gn == "decline")
+                        and kname in r.taps and r.taps[kname](tuple(k))):
+                    continue
+                d = conv_desc(x, x1, out, None, cout, k, stride, pad, up, up_mode, r.precision)
+                if not getattr(self.lib, r.ok)(C.byref(d)) or (r.splitk and self.split_small_grids and
+                                                                self.lib.sdc_conv_splitk_bytes(C.byref(d))):
+                    continue
+                wb = self.packed(lambda: r.pack(_val(src.w), src.kind, cout, c0 + c1, k))
                 self.keep += [d, x, x1, wb, bias, out]
-                nparts = int(self.lib.sdc_conv_gnparts(C.byref(d), gn_groups)) if (gn_groups and self.fuse_gn_stats) else 0
-                parts = None
-                if nparts > 0:
-                    parts = torch.empty(B * gn_groups * nparts * 2, dtype=torch.float64, device=self.device)
-                    self.keep.append(parts)
-                    self._gn_parts[out.data_ptr()] = (parts, nparts, gn_groups)
-                self._emit(self.lib.sdc_conv_wino3_x3, C.byref(d), _ptr(x), _ptr(x1), _ptr(wb), _ptr(bias), _ptr(out), _ptr(parts),
-                           gn_groups if nparts > 0 else 0)
+                parts = self._gn_partials(d, out, gn_groups) if r.gn == "sums" else None
+                self._emit(getattr(self.lib, r.fn), C.byref(d), _ptr(x), *([_ptr(x1)] if r.x1 else []), _ptr(wb), _ptr(bias), _ptr(out),
+                           *([_ptr(parts), gn_groups if parts is not None else 0] if r.gn == "sums" else []))
                 return out
-        if callable(wp):
-            wp = wp()
-        prec = conv_precision(wp.numel(), k, c0 + c1, cout, f16=self.precision)
+            w = self.conv_weight(src.w, src.kind)
+        prec = conv_precision(w.numel(), k, c0 + c1, cout, f16=self.precision)
         d = conv_desc(x, x1, out, residual, cout, k, stride, pad, up, up_mode, prec)
         if residual is not None:
             assert tuple(residual.shape) == tuple(out.shape)
-        self.keep += [d, x, x1, wp, bias, residual, out]     # the call list holds raw pointers only
+        self.keep += [d, x, x1, w, bias, residual, out]     # the call list holds raw pointers only
         if self.split_small_grids and residual is None:
             # a grid that leaves most of the chip idle (small batch, deep level): Cin split over several workgroups per tile.  The
             # statistics of a following GroupNorm then come from its own kernel (these tensors are small: sdc_gn_fused)
@@ -493,17 +525,14 @@ class Plan:
             if nsplit:
                 work = torch.empty(nsplit // 4, dtype=torch.float32, device=self.device)
                 self.keep.append(work)
-                self._emit(self.lib.sdc_conv_splitk, C.byref(d), _ptr(x), _ptr(x1), _ptr(wp), _ptr(bias), _ptr(out), _ptr(work), nsplit)
+                self._emit(self.lib.sdc_conv_splitk, C.byref(d), _ptr(x), _ptr(x1), _ptr(w), _ptr(bias), _ptr(out), _ptr(work), nsplit)
                 return out
-        nparts = int(self.lib.sdc_conv_gnparts(C.byref(d), gn_groups)) if (gn_groups and self.fuse_gn_stats) else 0
-        if nparts > 0:
-            parts = torch.empty(B * gn_groups * nparts * 2, dtype=torch.float64, device=self.device)
-            self.keep.append(parts)
-            self._gn_parts[out.data_ptr()] = (parts, nparts, gn_groups)
-            self._emit(self.lib.sdc_conv_gn, C.byref(d), _ptr(x), _ptr(x1), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(out),
+        parts = self._gn_partials(d, out, gn_groups)
+        if parts is not None:
+            self._emit(self.lib.sdc_conv_gn, C.byref(d), _ptr(x), _ptr(x1), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out),
                        _ptr(parts), gn_groups)
             return out
-        self._emit(self.lib.sdc_conv, C.byref(d), _ptr(x), _ptr(x1), _ptr(wp), _ptr(bias), _ptr(residual), _ptr(out))
+        self._emit(self.lib.sdc_conv, C.byref(d), _ptr(x), _ptr(x1), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out))
         return out
 
     def conv_transpose_422(self, x, w, bias, cout):
@@ -514,14 +543,8 @@ class Plan:
         out = self.pool.get((B, cout, iD, 2 * iH, 2 * iW))
         for ph in (0, 1):
             for pw in (0, 1):
-                kind = ("convT_sub", ph, pw)
-                if self.gemm_split:
-                    # (the usual buffer is packed only if the parity takes the usual path)
-                    self.conv(x, lambda kind=kind: self.conv_weight(w, kind), bias, cout, (1, 2, 2), pad=(0, 1 - ph, 1 - pw),
-                              out=out[:, :, :, ph::2, pw::2], gemm_w=lambda kind=kind: pack_conv_weight(w() if callable(w) else w, kind, 0))
-                    continue
-                wp = self.conv_weight(w, kind)
-                self.conv(x, wp, bias, cout, (1, 2, 2), pad=(0, 1 - ph, 1 - pw), out=out[:, :, :, ph::2, pw::2])
+                self.conv(x, WeightSrc(w, ("convT_sub", ph, pw)), bias, cout, (1, 2, 2), pad=(0, 1 - ph, 1 - pw),
+                          out=out[:, :, :, ph::2, pw::2])
         return out
 
     def upsample2_conv3(self, x, w, bias, cout):
@@ -531,8 +554,8 @@ class Plan:
         out = self.pool.get((B, cout, iD, 2 * iH, 2 * iW))
         for ph in (0, 1):
             for pw in (0, 1):
-                wp = self.conv_weight(w, ("up2_sub", ph, pw))
-                self.conv(x, wp, bias, cout, (1, 2, 2), pad=(0, 1 - ph, 1 - pw), out=out[:, :, :, ph::2, pw::2])
+                self.conv(x, WeightSrc(w, ("up2_sub", ph, pw)), bias, cout, (1, 2, 2), pad=(0, 1 - ph, 1 - pw),
+                          out=out[:, :, :, ph::2, pw::2])
         return out
 
     def gn_silu(self, x, gamma, beta, groups, *, ss=None, t_dev=None, ss_t_stride=0, ss_b_stride=0, ss_off=0,
@@ -642,41 +665,31 @@ class Plan:
         the fp32 packed weights, still serve its fp32 middle launch)."""
         Cc = x.shape[1]
         y = self.pool.get(tuple(x.shape))
-        if w16 is not None and self.linattn_f16_routes(Cc, n):
-            uq, uo = w16
-            wpk = self.packed(lambda: pack_linattn_f16(uq() if callable(uq) else uq, uo() if callable(uo) else uo))
-            work = torch.empty((int(self.lib.sdc_linattn_block_f16_bytes(outer, inner, Cc, n)) + 3) // 4, dtype=torch.float32, device=self.device)
-            self.keep += [x, g_pre, wqkv, wo, wpk, bo, g_post, work, y]
-            if gn is not None:
-                st, gamma, beta, groups, res = gn
-                assert outer == x.shape[0] and (res is None or (tuple(res.shape) == tuple(x.shape) and res.stride() == x.stride()))
-                self.keep += [st, gamma, beta, res]
-                self._emit(self.lib.sdc_linattn_block_gn_f16, _ptr(x), _ptr(st), _ptr(gamma), _ptr(beta), groups, _ptr(res), _ptr(g_pre),
-                           _ptr(wqkv), _ptr(wo), _ptr(wpk), _ptr(bo), _ptr(g_post), _ptr(work), _ptr(y), outer, inner, Cc, n, *strides,
-                           pre_mode, post_mode, eps)
-                return y
-            self._emit(self.lib.sdc_linattn_block_f16, _ptr(x), _ptr(g_pre), _ptr(wqkv), _ptr(wo), _ptr(wpk), _ptr(bo), _ptr(g_post),
-                       _ptr(work), _ptr(y), outer, inner, Cc, n, *strides, pre_mode, post_mode, eps)
-            return y
-        work = torch.empty(int(self.lib.sdc_linattn_block_bytes(outer, inner, Cc, n)) // 4, dtype=torch.float32, device=self.device)
-        self.keep += [x, g_pre, wqkv, wo, bo, g_post, work, y]
+        f16 = w16 is not None and self.linattn_f16_routes(Cc, n)
+        if f16:
+            wpk = self.packed(lambda: pack_linattn_f16(_val(w16[0]), _val(w16[1])))
+            nwork = (int(self.lib.sdc_linattn_block_f16_bytes(outer, inner, Cc, n)) + 3) // 4
+        else:
+            wpk, nwork = None, int(self.lib.sdc_linattn_block_bytes(outer, inner, Cc, n)) // 4
+        work = torch.empty(nwork, dtype=torch.float32, device=self.device)
+        self.keep += [x, g_pre, wqkv, wo, wpk, bo, g_post, work, y]
+        head = [_ptr(x)]
         if gn is not None:
             st, gamma, beta, groups, res = gn
             assert outer == x.shape[0] and (res is None or (tuple(res.shape) == tuple(x.shape) and res.stride() == x.stride()))
             self.keep += [st, gamma, beta, res]
-            self._emit(self.lib.sdc_linattn_block_gn, _ptr(x), _ptr(st), _ptr(gamma), _ptr(beta), groups, _ptr(res), _ptr(g_pre),
-                       _ptr(wqkv), _ptr(wo), _ptr(bo), _ptr(g_post), _ptr(work), _ptr(y), outer, inner, Cc, n, *strides, pre_mode,
-                       post_mode, eps)
-            return y
-        self._emit(self.lib.sdc_linattn_block, _ptr(x), _ptr(g_pre), _ptr(wqkv), _ptr(wo), _ptr(bo), _ptr(g_post), _ptr(work),
-                   _ptr(y), outer, inner, Cc, n, *strides, pre_mode, post_mode, eps)
+            head += [_ptr(st), _ptr(gamma), _ptr(beta), groups, _ptr(res)]
+        fn = ((self.lib.sdc_linattn_block, self.lib.sdc_linattn_block_f16),
+              (self.lib.sdc_linattn_block_gn, self.lib.sdc_linattn_block_gn_f16))[gn is not None][f16]
+        self._emit(fn, *head, _ptr(g_pre), _ptr(wqkv), _ptr(wo), *([_ptr(wpk)] if f16 else []), _ptr(bo), _ptr(g_post), _ptr(work), _ptr(y),
+                   outer, inner, Cc, n, *strides, pre_mode, post_mode, eps)
         return y
 
     def tattn_weight(self, wqkv, wo, split=False):
         """Register the fp16 buffer of the temporal-attention weights (pack_tattn_f16; split: the three bf16 planes of pack_tattn_x3)
         from the unpacked nn.Linear weights to_qkv / to_out (tensors or callables returning them), refreshed by refresh_weights()."""
         pack = pack_tattn_x3 if split else pack_tattn_f16
-        return self.packed(lambda: pack(wqkv() if callable(wqkv) else wqkv, wo() if callable(wo) else wo))
+        return self.packed(lambda: pack(_val(wqkv), _val(wo)))
 
     def tattn_split_routes(self, Cc, Fr, hw):
         """True where net.attn_split sends a fused temporal-attention site of width Cc, Fr frames and hw pixels per sample to
@@ -692,19 +705,13 @@ class Plan:
         assert x.is_contiguous()
         y = self.pool.get(tuple(x.shape))
         if self.tattn_split_routes(Cc, Fr, H * W):
-            wpk = self.tattn_weight(wqkv, wo, split=True)
-            self.keep += [x, g_pre, wpk, rot, bias, y]
-            self._emit(self.lib.sdc_tattn_block_x3, _ptr(x), _ptr(g_pre), _ptr(wpk), _ptr(rot), _ptr(bias), _ptr(y),
-                       B, H * W, Cc, Fr, Cc * Fr * H * W, Fr * H * W, H * W, eps)
-            return y
-        if self.attn_f16:
-            wpk = self.tattn_weight(wqkv, wo)
-            self.keep += [x, g_pre, wpk, rot, bias, y]
-            self._emit(self.lib.sdc_tattn_block_f16, _ptr(x), _ptr(g_pre), _ptr(wpk), _ptr(rot), _ptr(bias), _ptr(y),
-                       B, H * W, Cc, Fr, Cc * Fr * H * W, Fr * H * W, H * W, eps)
-            return y
-        self.keep += [x, g_pre, wqkv, wo, rot, bias, y]
-        self._emit(self.lib.sdc_tattn_block, _ptr(x), _ptr(g_pre), _ptr(wqkv), _ptr(wo), _ptr(rot), _ptr(bias), _ptr(y),
+            fn, w = self.lib.sdc_tattn_block_x3, [self.tattn_weight(wqkv, wo, split=True)]
+        elif self.attn_f16:
+            fn, w = self.lib.sdc_tattn_block_f16, [self.tattn_weight(wqkv, wo)]
+        else:
+            fn, w = self.lib.sdc_tattn_block, [wqkv, wo]
+        self.keep += [x, g_pre, *w, rot, bias, y]
+        self._emit(fn, _ptr(x), _ptr(g_pre), *map(_ptr, w), _ptr(rot), _ptr(bias), _ptr(y),
                    B, H * W, Cc, Fr, Cc * Fr * H * W, Fr * H * W, H * W, eps)
         return y
 

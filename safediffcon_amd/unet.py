@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from ._lib import check, get_lib
-from .engine import Plan, as5, pack_conv_weight
+from .engine import PLAN_SWITCHES, Plan, WeightSrc, as5
 
 HEADS, DIM_HEAD = 4, 32
 HID = HEADS * DIM_HEAD
@@ -226,22 +226,8 @@ class _Builder:
         if pad is None:
             pad = tuple(kk // 2 for kk in k)
         b = self.V(f"{prefix}.bias") if bias else None
-        if (self.plan.stem_f16 or self.plan.stem_split) and kind == "conv" and k[2] == 7:
-            # net.stem_f16 / net.stem_split: a 7-tap conv; Plan.conv asks the library whether the stem kernel covers it and packs the
-            # usual buffer only if not
-            return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up, residual=residual,
-                                  out=out, gn_groups=gn_groups, stem_w=lambda: self.net.P(wkey))
-        if self.plan.gemm_split and kind == "conv" and k in ((1, 4, 4), (1, 1, 1)) and x1 is None and residual is None:
-            # net.gemm_split: a strided or 1x1 conv; Plan.conv asks the library's routing table and packs the usual buffer only if the
-            # conv stays on the fp32 kernels
-            return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, stride=stride, pad=pad, up=up, out=out, gn_groups=gn_groups,
-                                  gemm_w=lambda: pack_conv_weight(self.net.P(wkey), kind, 0))
-        if self.plan.wino_split and kind == "conv" and k == (3, 3, 3) and residual is None:
-            # net.wino_split: a 3x3x3 conv; Plan.conv asks the library's routing table and packs the usual buffer only if the conv stays
-            # on the fp32 kernels
-            return self.plan.conv(x, lambda: self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up, out=out,
-                                  gn_groups=gn_groups, wino_w=lambda: pack_conv_weight(self.net.P(wkey), kind, 4))
-        return self.plan.conv(x, self.W(wkey, kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up,
+        # (which kernel runs the conv, and which buffer is packed for it, is Plan.conv's decision: engine.CONV_ROUTES)
+        return self.plan.conv(x, WeightSrc(lambda: self.net.P(wkey), kind), b, cout, k, x1=x1, stride=stride, pad=pad, up=up,
                               up_mode=1 if kind == "convT" else 0, residual=residual, out=out, gn_groups=gn_groups)
 
     def final_conv(self, res_prefix, conv_prefix, h, groups, x1, out):
@@ -527,10 +513,9 @@ class _HipUNet(nn.Module):
     def entry(self, shape, rows, lut=False):
         """Plan for an input of `shape` whose conditioning table has `rows` rows: one row per sample
         (lut=False, forward(x, time)) or one row per timestep read through a device-side t (lut=True, samplers)."""
+        switches = {name: bool(getattr(self, name)) for name in PLAN_SWITCHES}
         key = (tuple(shape), rows, bool(lut), int(self.precision), bool(self.fuse_linattn), bool(self.subpixel_upsample),
-               bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), bool(self.stem_f16),
-               bool(self.stem_split), bool(self.gemm_split), bool(self.attn_f16), bool(self.wino_split), bool(self.attn_split),
-               bool(self.linattn_f16))
+               bool(self.fuse_gn_into_linattn), bool(self.split_small_grids), bool(self.fuse_final_conv), *switches.values())
         stamp = self._weights_stamp()
         ent = self._plans.get(key)
         if ent is not None and ent["wstamp"] != stamp:        # parameters changed since this plan packed them
@@ -540,9 +525,7 @@ class _HipUNet(nn.Module):
             if dev.type != "cuda":
                 raise RuntimeError("safediffcon_amd runs on MI355X only: move the model to a cuda (HIP) device; "
                                    "there is no CPU fallback")
-            plan = Plan(dev, precision=self.precision, stem_f16=bool(self.stem_f16), stem_split=bool(self.stem_split),
-                        gemm_split=bool(self.gemm_split), attn_f16=bool(self.attn_f16), wino_split=bool(self.wino_split),
-                        attn_split=bool(self.attn_split), linattn_f16=bool(self.linattn_f16))
+            plan = Plan(dev, precision=self.precision, **switches)
             plan.split_small_grids = bool(self.split_small_grids)
             x = torch.zeros(shape, dtype=torch.float32, device=dev)
             eps = torch.zeros(shape, dtype=torch.float32, device=dev)

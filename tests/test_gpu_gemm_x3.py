@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 import safediffcon_amd as sdc
 from safediffcon_amd import _lib
-from safediffcon_amd.engine import Plan, conv_desc, pack_conv_weight, pack_gemm_x3
+from safediffcon_amd.engine import Plan, WeightSrc, conv_desc, pack_conv_weight, pack_gemm_x3
 from oracle.detweights import det_params, det_tensor
 
 pytestmark = pytest.mark.gpu
@@ -160,8 +160,7 @@ def test_gemm_x3_uncovered_descriptors():
     assert torch.isnan(y).all()                   # nothing was launched
     # a conv whose GroupNorm sums the epilogue could carry keeps the fp32 kernels: the plan records no split call for it
     plan = Plan(DEV, precision=4, gemm_split=True)
-    wp = torch.zeros(64, 64, device=DEV)
-    plan.conv(x, wp, None, 64, (1, 1, 1), gn_groups=8, gemm_w=lambda: wp)
+    plan.conv(x, WeightSrc(torch.zeros(64, 64, 1, 1, 1, device=DEV)), None, 64, (1, 1, 1), gn_groups=8)
     assert [fn.__name__ for fn, _ in plan.calls if "conv" in fn.__name__][0] in ("sdc_conv", "sdc_conv_gn")
     # (the covered descriptor runs)
     _lib.check(lib.sdc_conv_gemm_x3(C.byref(ok), x.data_ptr(), wb.data_ptr(), 0, y.data_ptr(), _stream()), "sdc_conv_gemm_x3")

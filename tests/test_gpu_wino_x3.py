@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 import safediffcon_amd as sdc
 from safediffcon_amd import _lib
-from safediffcon_amd.engine import Plan, conv_desc, pack_conv_weight, pack_wino3_x3
+from safediffcon_amd.engine import Plan, WeightSrc, conv_desc, pack_conv_weight, pack_wino3_x3
 from oracle.detweights import det_params, det_tensor
 
 pytestmark = pytest.mark.gpu
@@ -236,8 +236,7 @@ def test_wino_split_smoke_net_against_reference_fixture(golden):
     outs = {}
     for on in (False, True):
         plan = Plan(DEV, precision=4, wino_split=on)
-        wp4 = plan.conv_weight(w)
-        y = plan.conv(xx, wp4, None, 256, (3, 3, 3), pad=(1, 1, 1), gn_groups=8, wino_w=lambda: pack_conv_weight(w, "conv", 4))
+        y = plan.conv(xx, WeightSrc(w), None, 256, (3, 3, 3), pad=(1, 1, 1), gn_groups=8)
         z = plan.gn_silu(y, torch.ones(256, device=DEV), torch.zeros(256, device=DEV), 8, out=torch.empty_like(y))
         names = [fn.__name__ for fn, _ in plan.calls]
         listed = bool(lib.sdc_conv_wino3_x3_ok(plan.calls[0][1][0]))

@@ -1,5 +1,6 @@
 """CPU: the host side of net.wino_split (csrc/sdc_conv_wino_x3.hip) -- the exact three-way bf16 split, the packed weight layout of
 sdc_conv_wino3_x3 against a plain-loop reference, the size query, and the switch semantics of Plan and of the nets."""
+import ctypes as C
 import inspect
 
 import pytest
@@ -7,7 +8,7 @@ import torch
 
 import safediffcon_amd as sdc
 from safediffcon_amd import _lib, engine
-from safediffcon_amd.engine import Plan, pack_conv_weight, pack_wino3_x3, split3_bf16
+from safediffcon_amd.engine import PLAN_SWITCHES, Plan, pack_conv_weight, pack_wino3_x3, split3_bf16
 
 
 def test_split_is_exact_over_the_exponent_range():
@@ -98,22 +99,70 @@ def test_plan_switch_semantics():
         assert _plan(precision=prec, wino_split=True).wino_split is False
 
 
-def test_net_switch_is_on_and_part_of_the_plan_cache_key():
+@pytest.mark.parametrize("switch", PLAN_SWITCHES)
+def test_net_switch_is_on_and_part_of_the_plan_cache_key(switch, monkeypatch):
+    """entry() on a CPU box, up to the point where it builds the Plan: every switch of PLAN_SWITCHES is an attribute of the nets, one
+    element of the cache key, and reaches the Plan with the net's value"""
     for net in (sdc.Unet3D_with_Conv3D(dim=8, dim_mults=(1, 2), channels=7),
                 sdc.Unet2D(dim=8, dim_mults=(1, 2), channels=3, resnet_block_groups=1),
                 sdc.Unet1D(dim=8, dim_mults=(1, 2), channels=12, resnet_block_groups=1)):
         assert net.wino_split is WINO_DEFAULT
-    src = inspect.getsource(type(net).entry) if "wino_split" in inspect.getsource(type(net).entry) else inspect.getsource(sdc.unet)
-    key = src[src.index("key = ("):src.index("stamp = self._weights_stamp()")]
-    assert "bool(self.wino_split)" in key                     # part of the cache key
-    assert "wino_split=bool(self.wino_split)" in src          # handed to the Plan
+        assert isinstance(getattr(net, switch), bool)
+    assert switch in inspect.signature(Plan.__init__).parameters
+
+    class Stop(Exception):
+        pass
+
+    seen, made = [], []
+
+    class Keys(dict):
+        def get(self, key, default=None):
+            seen.append(key)
+            return super().get(key, default)
+
+    def fake_plan(dev, **kw):
+        made.append(kw)
+        raise Stop
+
+    class Dev:
+        type = "cuda"
+
+    net._plans = Keys()
+    monkeypatch.setattr(sdc.unet, "Plan", fake_plan)
+    monkeypatch.setattr(net, "device", lambda: Dev())
+    was = getattr(net, switch)
+    for on in (was, not was, was):
+        setattr(net, switch, on)
+        with pytest.raises(Stop):
+            net.entry((2, 12, 16), 2)
+    k_a, k_b, k_a2 = seen
+    assert k_a == k_a2 and k_a != k_b                         # part of the cache key
+    assert sum(a != b for a, b in zip(k_a, k_b)) == 1 and len(k_a) == len(k_b)
+    assert [kw[switch] for kw in made] == [was, not was, was]             # handed to the Plan
+    # the switch changes nothing else that the Plan is built with, and the Plan is built with every switch
+    assert {k: v for k, v in made[0].items() if k != switch} == {k: v for k, v in made[1].items() if k != switch}
+    assert set(made[0]) == {"precision", *PLAN_SWITCHES}
+
+
+def _recorded(net, shape, wino_split):
+    """the call list of net's plan at precision 4 -- (name, arguments) with descriptors as bytes and device pointers blanked -- and the
+    sorted sizes of its packed weight buffers"""
+    plan = Plan("cpu", precision=4, wino_split=wino_split)
+    x = torch.zeros(shape)
+    net._build(sdc.unet._Builder(net, plan), x, torch.zeros_like(x))
+    calls = [(fn.__name__, [bytes(a._obj) if ty is C.POINTER(_lib.SdcConvDesc) else None if ty is C.c_void_p else a
+                            for a, ty in zip(args, fn.argtypes)]) for fn, args in plan.calls]
+    return calls, sorted(dst.numel() for dst, _ in plan.repackers)
 
 
 def test_c2_c3_convs_never_ask_for_the_route():
-    # the 1-D and 2-D nets have no 3x3x3 conv: _Builder.conv hands wino_w only to (3, 3, 3) taps, so their plans record the parent's calls
-    src = inspect.getsource(sdc.unet._Builder.conv)
-    assert "k == (3, 3, 3)" in src and "wino_w=" in src
-    assert src.count("wino_w=") == 1
+    # the 1-D and 2-D nets have no 3x3x3 conv: with the switch on their plans record the calls of a plan with the switch off -- names,
+    # descriptors, scalar arguments and the sizes of the packed weight buffers -- and none of them is the split kernel
+    for net, shape in ((sdc.Unet2D(dim=64, dim_mults=(1, 2), channels=3, resnet_block_groups=1), (1, 3, 16, 128)),
+                       (sdc.Unet1D(dim=64, dim_mults=(1, 2), channels=12, resnet_block_groups=1), (1, 12, 128))):
+        on, off = _recorded(net, shape, True), _recorded(net, shape, False)
+        assert on == off and len(on[0]) > 50
+        assert "sdc_conv_wino3_x3" not in [name for name, _ in on[0]]
 
 
 WINO_DEFAULT = True

@@ -227,6 +227,23 @@ int sdc_linattn_block_gn(const float* x_raw, const float* gn_stats, const float*
                          const float* gn_residual, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
                          const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
                          int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream);
+/* The two entries above with the kernels chosen by hand (csrc/sdc_lablock_x3.hip): the same arguments with
+ * `impl` in front of the stream.  impl 0: every product on the fp32 matrix pipe.  impl 1: the two products with a weight operand,
+ * K^T = xn^T Wk^T of pass 1 and Q = Wq xn of pass 2, on the bf16 pipe from exact three-way bf16 splits of both operands (six terms, fp32
+ * accumulation: an fp32-grade result in another rounding order); the weights are split inside the kernels from the same packed wqkv,
+ * `work` and sdc_linattn_block_bytes are unchanged; everything else -- norms, softmaxes, M^T += xn p, la_blk_mid, y = T q, the residual
+ * -- is impl 0's code in impl 0's order.  A non-finite x gives NaN where impl 0 may give an infinity.  Any other impl: SDC_EINVAL,
+ * like a bad shape, before any launch.
+ * sdc_linattn_block_x3_ok(C, n): 1 at the (C, tokens per sequence) -- never the batch -- where impl 1 measured faster by the
+ * per-launch rule; sdc_linattn_block / sdc_linattn_block_gn are the _sel entries with impl = sdc_linattn_block_x3_ok(C, n). */
+int sdc_linattn_block_sel(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
+                          const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
+                          int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, int impl, void* stream);
+int sdc_linattn_block_gn_sel(const float* x_raw, const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_G,
+                             const float* gn_residual, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
+                             const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
+                             int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, int impl, void* stream);
+int sdc_linattn_block_x3_ok(int C, int64_t n);
 
 /* The same block with fp16 operands and fp32 accumulation (net.linattn_f16, opt-in, samplers only; DESIGN.md section 20;
  * csrc/sdc_lablock_f16.hip).  A switch of its own: sdc_linattn_block, sdc_linattn_block_gn and their buffers are untouched.  The same

@@ -93,6 +93,11 @@ SIGNATURES = {
                                     _i64, _i64, _i64, C.c_int, C.c_int, C.c_float, _stream]),
     "sdc_linattn_block_gn": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
                                        C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_float, _stream]),
+    "sdc_linattn_block_sel": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _i64,
+                                        _i64, _i64, _i64, C.c_int, C.c_int, C.c_float, C.c_int, _stream]),
+    "sdc_linattn_block_gn_sel": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                           C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_float, C.c_int, _stream]),
+    "sdc_linattn_block_x3_ok": (C.c_int, [C.c_int, _i64]),
     "sdc_pack_linattn_f16_bytes": (C.c_size_t, [C.c_int]),
     "sdc_pack_linattn_f16": (C.c_int, [_f32p, _f32p, C.c_int, C.c_void_p, _stream]),
     "sdc_linattn_block_f16_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, _i64]),

@@ -22,6 +22,7 @@
 // Every stage runs for every tile (a clipped kd adds exact zeros), no K split, no atomics: a sample's bits never depend on its tile
 // mates or on the batch.  Epilogue: bias, fp32 stores through the descriptor's strides.
 #include "sdc_conv.h"
+#include "sdc_split3.h"
 
 using namespace sdcconv;
 
@@ -44,15 +45,6 @@ struct StemX3Args {
     int itemsB;               // NR * W staged positions
     int plane;                // bf16 elements of one weight piece: kD * NS * Cout * 16
 };
-
-// x = h + m + l exactly (finite x): hardware RNE conversions, exact fp32 residuals
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-#pragma clang fp contract(off)
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
-}
 
 // KH = 7: 7x7 taps per kd plane; KH = 1: 1x7 taps.  ITB: staged positions per thread (NR * W <= ITB * 256).
 // The five small terms of a product go to accumulators of their own (sm), added to the main ones once at the end.  Every MFMA rounds

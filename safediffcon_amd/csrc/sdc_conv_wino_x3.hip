@@ -27,6 +27,7 @@
 // sample's bits do not depend on its batch or its tile mates.  A non-finite input gives NaN where the fp32 kernel gives +-inf (inf - inf
 // in the split residuals, 0 * inf in a clipped plane).
 #include "sdc_conv.h"
+#include "sdc_split3.h"
 
 using namespace sdcconv;
 
@@ -93,13 +94,6 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
 }
 __device__ __forceinline__ float bf16_lo(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-#pragma clang fp contract(off)
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
-}
 
 constexpr int X3_BM = 64, X3_TILES = 64, X3_SK = 16;
 constexpr int X3_PC = 4 * 64 * X3_SK * 2;        // bytes of one piece of a sub-stage image: [4 xi][64 rows][16 ci] bf16

@@ -19,27 +19,6 @@
 
 namespace {
 
-struct LaArgs {
-    const float* x;
-    const float* g_pre;
-    const float* wqkv;      // packed [C][384]  (q | k | v, each heads*32)
-    const float* wo;        // packed [128][C]
-    const float* bo;        // [C] or null
-    const float* g_post;    // [C] or null
-    float* part;            // [nseq][nsplit][4][32*(C+2)]
-    float* tt;              // [nseq][128][C]
-    float* y;
-    // GroupNorm + SiLU (+ residual) of the producing ResnetBlock applied on load (sdc_linattn_block_gn): x is then the RAW conv
-    // output, gn_stats (mean, rstd) per (outer index, group), gn_res the residual branch (same strides as x) or null
-    const float* gn_stats; const float* gn_gamma; const float* gn_beta; const float* gn_res;
-    float* gn_hout;         // pass 1 stores h here (x's strides); pass 2 then reads it as its x
-    int gn_G;
-    int inner, nsplit, tiles_per_split, ntiles, tiles_per_blk;
-    int pre_mode, post_mode;
-    float eps;
-    int64_t so, sc, si;
-};
-
 // x tile (C channels x 64 tokens) -> channel norm over C per token -> xs[c][tok].  Thread (tok = tid & 63, group =
 // tid >> 6) owns C/4 channels of one token; the per-token statistics are combined across the 4 groups through `red`.
 // mode 0: (x - mean) * rsqrt(var + eps) * g (two-pass variance); mode 1: x / max(||x||, 1e-12) * g * sqrt(C).
@@ -460,8 +439,10 @@ namespace {
 int linattn_block_impl(const float* x, const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_G,
                        const float* gn_res, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
                        const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
-                       int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream) {
+                       int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, int impl, void* stream) {
     SDC_REQUIRE(x && g_pre && wqkv && wo && work && y, SDC_ENULL, "sdc_linattn_block: null pointer");
+    // impl 0: every product on the fp32 pipe (la_blk_ctx / la_blk_out); 1: the q / k projections as bf16 splits (sdc_lablock_x3.hip)
+    SDC_REQUIRE(impl == 0 || impl == 1, SDC_EINVAL, "sdc_linattn_block: impl must be 0 or 1 (got %d)", impl);
     SDC_REQUIRE(C == 64 || C == 128, SDC_EINVAL, "sdc_linattn_block: dim must be 64 or 128 (got %d)", C);
     SDC_REQUIRE(outer > 0 && inner > 0 && n > 0 && n % TT == 0, SDC_EINVAL, "sdc_linattn_block: tokens must be a multiple of 64");
     SDC_REQUIRE((pre_mode == 0 || pre_mode == 1) && post_mode >= -1 && post_mode <= 1, SDC_EINVAL, "sdc_linattn_block: bad norm mode");
@@ -500,7 +481,14 @@ int linattn_block_impl(const float* x, const float* gn_stats, const float* gn_ga
     const bool gn = gn_stats != nullptr;
     LaArgs a2 = a;                                  // pass 2 of the GroupNorm-on-load form: x = the h pass 1 left in y
     if (gn) { a.gn_hout = y; a2.x = y; a2.gn_stats = nullptr; }
-    if (C == 64) {
+    if (impl == 1) {
+        int rc = sdc::la_x3_launch_ctx(a, C, gn, g1, s);
+        if (rc != SDC_OK) return rc;
+        if (C == 64) hipLaunchKernelGGL(la_blk_mid<64>, gm, dim3(NT), 0, s, a);
+        else hipLaunchKernelGGL(la_blk_mid<128>, gm, dim3(NT), 0, s, a);
+        rc = sdc::la_x3_launch_out(a2, C, g2, s);
+        if (rc != SDC_OK) return rc;
+    } else if (C == 64) {
         if (gn) hipLaunchKernelGGL((la_blk_ctx<64, true>), g1, dim3(NT), ldsb, s, a);
         else hipLaunchKernelGGL((la_blk_ctx<64, false>), g1, dim3(NT), ldsb, s, a);
         hipLaunchKernelGGL(la_blk_mid<64>, gm, dim3(NT), 0, s, a);
@@ -515,19 +503,34 @@ int linattn_block_impl(const float* x, const float* gn_stats, const float* gn_ga
 }
 }  // namespace
 
+extern "C" int sdc_linattn_block_sel(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
+                                     const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
+                                     int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, int impl, void* stream) {
+    return linattn_block_impl(x, nullptr, nullptr, nullptr, 0, nullptr, g_pre, wqkv, wo, bo, g_post, work, y, outer, inner, C, n, so, sc,
+                              si, pre_mode, post_mode, eps, impl, stream);
+}
+
 extern "C" int sdc_linattn_block(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
                                  const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
                                  int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream) {
-    return linattn_block_impl(x, nullptr, nullptr, nullptr, 0, nullptr, g_pre, wqkv, wo, bo, g_post, work, y, outer, inner, C, n, so, sc,
-                              si, pre_mode, post_mode, eps, stream);
+    return sdc_linattn_block_sel(x, g_pre, wqkv, wo, bo, g_post, work, y, outer, inner, C, n, so, sc, si, pre_mode, post_mode, eps,
+                                 sdc_linattn_block_x3_ok(C, n), stream);
+}
+
+extern "C" int sdc_linattn_block_gn_sel(const float* x_raw, const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_G,
+                                        const float* gn_residual, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
+                                        const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
+                                        int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, int impl, void* stream) {
+    SDC_REQUIRE(gn_stats && gn_gamma && gn_beta, SDC_ENULL, "sdc_linattn_block_gn: null GroupNorm pointer");
+    SDC_REQUIRE(gn_G > 0 && (C == 64 || C == 128) && C % gn_G == 0, SDC_EINVAL, "sdc_linattn_block_gn: groups must divide the channels");
+    return linattn_block_impl(x_raw, gn_stats, gn_gamma, gn_beta, gn_G, gn_residual, g_pre, wqkv, wo, bo, g_post, work, y, outer, inner,
+                              C, n, so, sc, si, pre_mode, post_mode, eps, impl, stream);
 }
 
 extern "C" int sdc_linattn_block_gn(const float* x_raw, const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_G,
                                     const float* gn_residual, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
                                     const float* g_post, float* work, float* y, int outer, int inner, int C, int64_t n,
                                     int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream) {
-    SDC_REQUIRE(gn_stats && gn_gamma && gn_beta, SDC_ENULL, "sdc_linattn_block_gn: null GroupNorm pointer");
-    SDC_REQUIRE(gn_G > 0 && (C == 64 || C == 128) && C % gn_G == 0, SDC_EINVAL, "sdc_linattn_block_gn: groups must divide the channels");
-    return linattn_block_impl(x_raw, gn_stats, gn_gamma, gn_beta, gn_G, gn_residual, g_pre, wqkv, wo, bo, g_post, work, y, outer, inner,
-                              C, n, so, sc, si, pre_mode, post_mode, eps, stream);
+    return sdc_linattn_block_gn_sel(x_raw, gn_stats, gn_gamma, gn_beta, gn_G, gn_residual, g_pre, wqkv, wo, bo, g_post, work, y, outer,
+                                    inner, C, n, so, sc, si, pre_mode, post_mode, eps, sdc_linattn_block_x3_ok(C, n), stream);
 }

@@ -1,9 +1,42 @@
 // Tile helpers shared by the fused LinearAttention block kernels (sdc_lablock.hip: fp32 operands; sdc_lablock_f16.hip: fp16
-// operands): the tile geometry, the wave-uniform-base global accesses, the tile fetch and the GroupNorm-on-load arithmetic.
+// operands; sdc_lablock_x3.hip: bf16-split q / k projections): the kernel arguments, the tile geometry, the wave-uniform-base global
+// accesses, the tile fetch and the GroupNorm-on-load arithmetic.
 #pragma once
 #include "sdc_common.h"
 
+namespace sdc {
+
+struct LaArgs {
+    const float* x;
+    const float* g_pre;
+    const float* wqkv;      // packed [C][384]  (q | k | v, each heads*32)
+    const float* wo;        // packed [128][C]
+    const float* bo;        // [C] or null
+    const float* g_post;    // [C] or null
+    float* part;            // [nseq][nsplit][4][32*(C+2)]
+    float* tt;              // [nseq][128][C]
+    float* y;
+    // GroupNorm + SiLU (+ residual) of the producing ResnetBlock applied on load (sdc_linattn_block_gn): x is then the RAW conv
+    // output, gn_stats (mean, rstd) per (outer index, group), gn_res the residual branch (same strides as x) or null
+    const float* gn_stats; const float* gn_gamma; const float* gn_beta; const float* gn_res;
+    float* gn_hout;         // pass 1 stores h here (x's strides); pass 2 then reads it as its x
+    int gn_G;
+    int inner, nsplit, tiles_per_split, ntiles, tiles_per_blk;
+    int pre_mode, post_mode;
+    float eps;
+    int64_t so, sc, si;
+};
+
+// passes 1 and 3 of the block with the q / k projections as three-way bf16 splits (sdc_lablock_x3.hip), launched by
+// sdc_linattn_block_sel / sdc_linattn_block_gn_sel (sdc_lablock.hip) around la_blk_mid: the grids and arguments of la_blk_ctx / la_blk_out
+int la_x3_launch_ctx(const LaArgs& a, int C, bool gn, dim3 grid, hipStream_t stream);
+int la_x3_launch_out(const LaArgs& a, int C, dim3 grid, hipStream_t stream);
+
+}  // namespace sdc
+
 namespace {
+
+using sdc::LaArgs;
 
 constexpr int NT = 256;
 constexpr int TT = 64;            // tokens per tile

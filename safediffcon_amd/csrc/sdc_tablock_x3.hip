@@ -25,6 +25,7 @@
 // No atomics, fixed accumulation order, a sample's arithmetic does not see the batch.  A non-finite x gives NaN (inf - inf in the
 // residual of the split) where the fp32 kernel may give an infinity.
 #include "sdc_common.h"
+#include "sdc_split3.h"
 
 namespace {
 
@@ -75,15 +76,6 @@ __device__ __forceinline__ ta2 ta_rot(ta2 x, ta2 cs) {
 #pragma clang fp contract(off)
     const float t0 = x.x * cs.x, t1 = x.y * cs.x;
     return ta2{__builtin_fmaf(-x.y, cs.y, t0), __builtin_fmaf(x.x, cs.y, t1)};
-}
-
-// x = h + m + l exactly (finite x): hardware RNE conversions, exact fp32 residuals
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-#pragma clang fp contract(off)
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
 }
 
 __global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {

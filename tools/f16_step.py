@@ -42,6 +42,10 @@
       sdc_linattn_block / _gn against sdc_linattn_block_f16 / _gn_f16 on the same buffers, the medians of 20 launches in three interleaved
       repeats (the rule of DESIGN section 15); then the C4 sampler step, precision 4 against 4 + linattn_f16 and 6 + stem_f16 + attn_f16
       against the same + linattn_f16, the four arms interleaved round by round, and the C2 step, 4 against 4 + linattn_f16
+  python tools/f16_step.py --linattn-split [--no-step]
+      the fused LinearAttention block with its q / k projections as exact bf16 splits (csrc/sdc_lablock_x3.hip):
+      sdc_linattn_block_sel / _gn_sel with impl 0 against impl 1 on the same buffers at the sites of --linattn, the medians of 20
+      launches in three interleaved repeats; a size qualifies for sdc_linattn_block_x3_ok when every repeat beats every repeat
   python tools/f16_step.py --drift [T] --linattn
       the T-step guided smoke trajectories with precision 4 + net.linattn_f16 against 4
   python tools/f16_step.py --attn-split [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
@@ -471,6 +475,54 @@ def linattn_shapes():
         torch.cuda.empty_cache()
 
 
+def linattn_split_shapes():
+    """the fused LinearAttention block with its q / k projections as bf16 splits (csrc/sdc_lablock_x3.hip): sdc_linattn_block_sel /
+    sdc_linattn_block_gn_sel with impl 0 against impl 1 on the same buffers, at the sites of linattn_shapes(); the medians of 20 launches,
+    three interleaved repeats; a size QUALIFIES for sdc_linattn_block_x3_ok when every repeat of impl 1 beats every repeat of impl 0"""
+    from safediffcon_amd.engine import pack_conv_weight
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    torch.manual_seed(0)
+    # (the C4 up path has a width-64 block at 32 x 32 and a width-128 block at 16 x 16 besides the sites of linattn_shapes())
+    sites = [(64, 32, 64, 4096, True, 0, -1), (64, 32, 64, 4096, False, 0, -1), (64, 32, 128, 1024, True, 0, -1),
+             (64, 32, 64, 1024, True, 0, -1), (64, 32, 128, 256, True, 0, -1),
+             (256, 1, 64, 2048, False, 0, 0), (256, 1, 128, 512, False, 0, 0),
+             (2, 32, 64, 4096, True, 0, -1), (2, 32, 128, 1024, True, 0, -1), (2, 32, 64, 1024, True, 0, -1), (2, 32, 128, 256, True, 0, -1),
+             (2, 1, 64, 2048, False, 0, 0), (2, 1, 128, 512, False, 0, 0)]
+    for outer, inner, Cc, n, gn, pre, post in sites:
+        wqkv, wo = torch.randn(384, Cc, device=DEV) * 0.2, torch.randn(Cc, 128, device=DEV) * 0.1
+        g1, g2, bo = torch.rand(Cc, device=DEV) + 0.5, torch.rand(Cc, device=DEV) + 0.5, torch.randn(Cc, device=DEV) * 0.1
+        wq4, wo4 = pack_conv_weight(wqkv.view(384, Cc, 1)), pack_conv_weight(wo.view(Cc, 128, 1))
+        x = torch.randn(outer, Cc, inner, n, device=DEV) * 0.5
+        y0, y1 = torch.empty_like(x), torch.empty_like(x)
+        work = torch.empty(int(lib.sdc_linattn_block_bytes(outer, inner, Cc, n)) // 4, device=DEV)
+        gp = g2.data_ptr() if post >= 0 else None
+        head = (x.data_ptr(),)
+        if gn:
+            st = torch.stack((torch.randn(outer * 8, device=DEV) * 0.1, torch.rand(outer * 8, device=DEV) + 0.5), -1).reshape(-1).contiguous()
+            gam, bet, res = torch.rand(Cc, device=DEV) + 0.5, torch.randn(Cc, device=DEV) * 0.1, torch.randn_like(x) * 0.5
+            head = (x.data_ptr(), st.data_ptr(), gam.data_ptr(), bet.data_ptr(), 8, res.data_ptr())
+        tail = (outer, inner, Cc, n, Cc * inner * n, inner * n, n, pre, post, 1e-5)
+        f = lib.sdc_linattn_block_gn_sel if gn else lib.sdc_linattn_block_sel
+        a0 = (*head, g1.data_ptr(), wq4.data_ptr(), wo4.data_ptr(), bo.data_ptr(), gp, work.data_ptr(), y0.data_ptr(), *tail, 0)
+        a1 = (*head, g1.data_ptr(), wq4.data_ptr(), wo4.data_ptr(), bo.data_ptr(), gp, work.data_ptr(), y1.data_ptr(), *tail, 1)
+        m0, m1 = [], []
+        for _ in range(3):          # interleaved repeats of the median of 20: their spread is what a gain has to beat
+            m0.append(_time_call(f, a0, stream))
+            m1.append(_time_call(f, a1, stream))
+        # the branch y - h on sequence block 0 (the plain form: h = x)
+        br = y0[:1].double()
+        err = (y1[:1].double() - br).pow(2).mean().sqrt().item() / (br - (0 if gn else x[:1].double())).pow(2).mean().sqrt().item()
+        med0, med1 = statistics.median(m0), statistics.median(m1)
+        listed = bool(lib.sdc_linattn_block_x3_ok(Cc, n))
+        print(f"[measured] linattn block {'gn ' if gn else ''}outer {outer} inner {inner} C {Cc} n {n} ({'listed' if listed else 'not listed'}): "
+              f"impl 0 (fp32) {' / '.join(f'{v * 1e3:.1f}' for v in m0)} us | impl 1 (bf16-split q / k) {' / '.join(f'{v * 1e3:.1f}' for v in m1)} us"
+              f" -> x{med0 / med1:.2f} {'QUALIFIES (every repeat beats every repeat)' if max(m1) < min(m0) else 'does NOT qualify'}; "
+              f"rms difference on sample 0 of y{'' if gn else ', of the attention branch'}: {err:.2e}", flush=True)
+        del x, y0, y1, work
+        torch.cuda.empty_cache()
+
+
 def attn_split_shapes():
     """net.attn_split: sdc_tattn_block against sdc_tattn_block_x3 on the same buffers at the sites of the dim-64 smoke net -- 64 x 64 (the
     C4 site, B = 64 and B = 2), 32 x 32 and 16 x 16 (B = 64); the medians of 20 launches, three interleaved repeats; a shape QUALIFIES
@@ -547,12 +599,19 @@ if __name__ == "__main__":
     ap.add_argument("--wino", action="store_true", help="net.wino_split: the covered 3x3x3 convs, launch by launch, and the C4 step with the switch off / on")
     ap.add_argument("--attn", action="store_true", help="net.attn_f16: the block launch and the C4 step (with --drift: 4 + attn_f16 against 4)")
     ap.add_argument("--linattn", action="store_true", help="net.linattn_f16: the block launch at the C4 / C2 sites, the C4 and C2 steps (with --drift: 4 + linattn_f16 against 4)")
+    ap.add_argument("--linattn-split", action="store_true", help="the fused LinearAttention block, impl 0 (fp32) against impl 1 (bf16-split q / k projections) launch by launch; then the C4 and C2 steps of this build (the A/B is by commit: SDC_LIB_PATH)")
     ap.add_argument("--attn-split", action="store_true", help="net.attn_split: the block launch at the sites of the dim-64 smoke net and the C4 step with the switch off / on")
     ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --wino / --attn / --attn-split: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
         drift(a.drift, a.stem, a.attn, a.linattn)
+    elif a.linattn_split:
+        linattn_split_shapes()
+        if not a.no_step:
+            # the entry points carry no switch: the step's A/B is by commit (bench.py of the two checkouts, or SDC_LIB_PATH naming the
+            # parent's library for a second run of this command)
+            step_ab([w for w in wls if w in ("c4", "c2")], a.steps, a.warmup, a.rounds, arms=[4])
     elif a.linattn:
         linattn_shapes()
         if not a.no_step:

@@ -27,12 +27,11 @@
 // Epilogue as sdc_conv: bias, optional fp32 residual, fp32 output through the descriptor's strides, and (sdc_conv_gn) the fp64
 // GroupNorm partial sums where the tile grid lines up with (sample, group): S % 256 == 0, or whole samples of 64 / 128 positions per tile.
 #include "sdc_conv.h"
+#include "sdc_f16frag.h"
 
 using namespace sdcconv;
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 constexpr int F16_BM = 64, F16_BN = 256, F16_NT = 256;
 

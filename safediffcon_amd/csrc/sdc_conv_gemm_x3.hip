@@ -1,6 +1,6 @@
 // net.gemm_split (default on at precision >= 4, samplers only): the strided (1,4,4)/(1,2,2) convs, the 1x2x2 sub-pixel convs of the
 // transposed convs and the 1x1x1 convs as an implicit GEMM on v_mfma_f32_32x32x16_bf16 with EXACT three-way bf16 operand splits -- the
-// arithmetic of conv_stem_x3_kernel (sdc_conv_stem_x3.hip): fp32 inputs, fp32 accumulation, fp32 outputs, x = h + m + l with h = bf16(x),
+// arithmetic of conv_stem_x3_kernel (sdc_conv_stem_x3.hip; split3, split3x8 and the term order are sdc_split3.h's): fp32 inputs, fp32 accumulation, fp32 outputs, x = h + m + l with h = bf16(x),
 // m = bf16(x - h), l = bf16(x - h - m) (RNE, contraction off), six MFMAs per product, smallest terms first, the five small terms in
 // accumulators of their own that are added to the main ones once at the end.
 //
@@ -24,12 +24,11 @@
 // Every stage runs for every tile, fixed k order, no K split, no atomics: a sample's bits never depend on its tile mates or on the batch.
 // Epilogue: bias, fp32 stores through the descriptor's strides (the parity views of form 1 are strided along H and W).
 #include "sdc_conv.h"
+#include "sdc_split3.h"
 
 using namespace sdcconv;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int GX_BM = 64, GX_BN = 256, GX_NT = 256;
 
@@ -51,15 +50,6 @@ template <int FORM> struct GxForm;
 template <> struct GxForm<0> { static constexpr int TAPS = 16, NCB = 1, SS = 4, SH = 2, NPAR = 2; };
 template <> struct GxForm<1> { static constexpr int TAPS = 4, NCB = 2, SS = 8, SH = 1, NPAR = 1; };
 template <> struct GxForm<2> { static constexpr int TAPS = 1, NCB = 4, SS = 4, SH = 1, NPAR = 1; };
-
-// x = h + m + l exactly (finite x): hardware RNE conversions, exact fp32 residuals
-__device__ __forceinline__ void gx_split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-#pragma clang fp contract(off)
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
-}
 
 // ITB: staged 16-byte items per thread (2 NCB NR iW <= ITB * 256).  128 accumulator registers: one workgroup per CU.
 // Up to 9 items the next stage's rows are held in registers during this stage's MFMAs; the 12-item instance (planes of a few rows,
@@ -151,8 +141,7 @@ __global__ __launch_bounds__(GX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
         for (int k = 0; k < ITB; ++k) {
             if (tid + k * GX_NT < a.itemsB) {
                 bf16x8 h, m, l;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { __bf16 ph, pm, pl; gx_split3(bv[k][i], ph, pm, pl); h[i] = ph; m[i] = pm; l[i] = pl; }
+                split3x8(bv[k], h, m, l);
                 *reinterpret_cast<bf16x8*>(lds + bdst[k]) = h;
                 *reinterpret_cast<bf16x8*>(lds + bdst[k] + BIMG) = m;
                 *reinterpret_cast<bf16x8*>(lds + bdst[k] + 2 * BIMG) = l;
@@ -232,8 +221,7 @@ __global__ __launch_bounds__(GX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int p = 0; p < 3; ++p) bf[j][p] = *reinterpret_cast<const bf16x8*>(lds + bB[j] + tb + p * BIMG);
-                // smallest terms first: a3 b1, a2 b2, a1 b3, a2 b1, a1 b2, a1 b1; the four accumulators take each term in turn
-                constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+                // the six terms in sdc_split3.h's order (smallest first); the four accumulators take each term in turn
 #pragma unroll
                 for (int t = 0; t < 6; ++t)
 #pragma unroll
@@ -241,7 +229,7 @@ __global__ __launch_bounds__(GX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
                             f32x16& c = t < 5 ? sm[i][j] : acc[i][j];
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[t]], bf[j][PB[t]], c, 0, 0, 0);
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][X3_PA[t]], bf[j][X3_PB[t]], c, 0, 0, 0);
                         }
             }
         }
@@ -296,7 +284,7 @@ __global__ __launch_bounds__(256) void pack_gemm_x3_kernel(const float* __restri
     const int cbk = ks / taps, tap = ks - cbk * taps;
     const int ci = (st * ncb + cbk) * 16 + c16, co = mt * 64 + col;
     __bf16 ph, pm, pl;
-    gx_split3(wp[((int64_t)tap * Cin + ci) * Cout + co], ph, pm, pl);
+    split3(wp[((int64_t)tap * Cin + ci) * Cout + co], ph, pm, pl);
     out[e] = ph; out[n + e] = pm; out[2 * n + e] = pl;
 }
 

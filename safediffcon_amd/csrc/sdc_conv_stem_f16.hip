@@ -22,47 +22,33 @@
 // with it a sample's bits, never depend on its tile mates or on the batch.
 // Stage = one kd plane: the next plane's global loads (weights and rows) are issued before this plane's MFMAs; two workgroups per CU.
 // No K split, no atomics.  Epilogue: bias, fp32 stores through the descriptor's strides.
+// The tile geometry, the common arguments with their host fill, a workgroup's tile and the launch ladder are in sdc_conv_stem_tile.h,
+// shared with the bf16-split variant (sdc_conv_stem_x3.hip).
 #include "sdc_conv.h"
+#include "sdc_conv_stem_tile.h"
+#include "sdc_f16frag.h"
 
 using namespace sdcconv;
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-constexpr int SF_BM = 64, SF_BN = 256, SF_NT = 256;
-
-struct StemArgs {
-    const float* x;
-    const _Float16* wh;
-    const float* bias;
-    float* y;
-    int64_t xs[5], ys[5];
-    int B, Cin, Cout, oD, oH, W, lgW;
-    int kD;
-    int Hs, NR;               // rows of a plane a tile can hold, staged slot rows (planes a tile can touch * (Hs + KH - 1))
-    int Ntot, ntiles, mtiles;
-    int itemsB;               // NR * W staged positions
-};
+struct StemArgs { STEM_TILE_ARGS(_Float16, wh) };
 
 // KH = 7: 7x7 taps per kd plane; KH = 1: 1x7 taps.  ITB: staged positions per thread (NR * W <= ITB * 256)
 template <int KH, int ITB>
-__global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ? 1 : 2))) SDC_NO_DS_MERGE void conv_stem_f16_kernel(const StemArgs a) {
+__global__ __launch_bounds__(STEM_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ? 1 : 2))) SDC_NO_DS_MERGE void conv_stem_f16_kernel(const StemArgs a) {
     constexpr int TAPS = KH * 7;
     constexpr int NS = (TAPS + 1) / 2;                          // 16-deep MFMA steps per kd plane
     constexpr int HH = KH - 1;                                  // halo rows per plane group
-    constexpr int ASZ = NS * SF_BM * 32;                        // bytes of the A image
-    constexpr int ITA = (NS * SF_BM * 2 + SF_NT - 1) / SF_NT;   // 16-byte A items per thread
+    constexpr int ASZ = NS * STEM_BM * 32;                        // bytes of the A image
+    constexpr int ITA = (NS * STEM_BM * 2 + STEM_NT - 1) / STEM_NT;   // 16-byte A items per thread
     extern __shared__ __attribute__((aligned(16))) char lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     const int W = a.W, RP = W + 6;                              // LDS row pitch in positions
-    const int logical = xcd_tile(blockIdx.x, a.ntiles * a.mtiles);
-    const int mt = logical % a.mtiles, nt = logical / a.mtiles;
-    const int m0 = mt * SF_BM, n0 = nt * SF_BN;
-    const int r0 = n0 >> a.lgW;                                 // first row of the tile in the (b, od, oh) walk
-    const int plane0 = r0 / a.oH, oh0 = r0 - plane0 * a.oH;
+    const StemTile t = stem_tile(a);
+    const int m0 = t.m0, n0 = t.n0, r0 = t.r0, plane0 = t.plane0, oh0 = t.oh0;
     const int GR = a.Hs + HH;                                   // slot rows per plane group
 
     // ---- per-thread B staging items: (slot row sr, column w), w fastest; bases without the depth-tap part
@@ -71,7 +57,7 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ?
     bool bok[ITB];
 #pragma unroll
     for (int k = 0; k < ITB; ++k) {
-        const int it = tid + k * SF_NT;
+        const int it = tid + k * STEM_NT;
         const int w = it & (W - 1);
         const int sr = it >> a.lgW;
         int pl, ih;
@@ -88,8 +74,8 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ?
     int aoff[ITA];
 #pragma unroll
     for (int k = 0; k < ITA; ++k) {
-        const int it = tid + k * SF_NT;
-        const int s = it / (2 * SF_BM), r = it - s * (2 * SF_BM);
+        const int it = tid + k * STEM_NT;
+        const int s = it / (2 * STEM_BM), r = it - s * (2 * STEM_BM);
         aoff[k] = (s * a.Cout + m0) * 16 + r * 8;               // halves; + kd * NS * Cout * 16 per stage
     }
 
@@ -100,7 +86,7 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ?
 #pragma unroll
         for (int k = 0; k < ITA; ++k) {
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (tid + k * SF_NT < NS * SF_BM * 2) v = *reinterpret_cast<const uint4*>(a.wh + wst + aoff[k]);
+            if (tid + k * STEM_NT < NS * STEM_BM * 2) v = *reinterpret_cast<const uint4*>(a.wh + wst + aoff[k]);
             av[k] = v;
         }
         const int dk = kd - a.kD / 2;
@@ -116,10 +102,10 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ?
     auto store_stage = [&]() {
 #pragma unroll
         for (int k = 0; k < ITA; ++k)
-            if (tid + k * SF_NT < NS * SF_BM * 2) *reinterpret_cast<uint4*>(lds + (tid + k * SF_NT) * 16) = av[k];
+            if (tid + k * STEM_NT < NS * STEM_BM * 2) *reinterpret_cast<uint4*>(lds + (tid + k * STEM_NT) * 16) = av[k];
 #pragma unroll
         for (int k = 0; k < ITB; ++k) {
-            if (tid + k * SF_NT < a.itemsB) {
+            if (tid + k * STEM_NT < a.itemsB) {
                 half8 h;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) h[i] = (_Float16)bv[k][i];       // RNE (v_cvt_pk_f16_f32)
@@ -129,7 +115,7 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ?
     };
 
     // zero halo columns 0..2 and W+3..W+5 of every slot row (never overwritten: the staged columns are 3..W+2)
-    for (int e = tid; e < a.NR * 6; e += SF_NT) {
+    for (int e = tid; e < a.NR * 6; e += STEM_NT) {
         const int sr = e / 6, c = e - sr * 6;
         *reinterpret_cast<uint4*>(lds + ASZ + (sr * RP + (c < 3 ? c : W + c)) * 16) = make_uint4(0u, 0u, 0u, 0u);
     }
@@ -178,7 +164,7 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(ITB > 4 ?
             const int tb = kh * rowb + kw * 16;
             half8 af[2], bf[2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const half8*>(lds + (s * SF_BM + 32 * i) * 32 + aoffr);
+            for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const half8*>(lds + (s * STEM_BM + 32 * i) * 32 + aoffr);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int bs = (s == NS - 1) ? bC[j] : (kw == 6 ? bB[j] : bA[j]);
@@ -246,7 +232,7 @@ namespace sdcconv {
 
 StemShape stem_shape(const SdcConvDesc& d) {
     StemShape sh{};
-    const int W = d.oW, R = SF_BN / W, NS = (d.kH * 7 + 1) / 2;
+    const int W = d.oW, R = STEM_BN / W, NS = (d.kH * 7 + 1) / 2;
     if (d.kH == 1) { sh.Hs = R; sh.NG = 1; }
     else {
         sh.Hs = d.oH < R ? d.oH : R;
@@ -257,7 +243,7 @@ StemShape stem_shape(const SdcConvDesc& d) {
     }
     sh.NR = sh.NG * (sh.Hs + d.kH - 1);
     sh.itemsB = sh.NR * W;
-    sh.lds = (size_t)NS * SF_BM * 32 + (size_t)sh.NR * (W + 6) * 16;
+    sh.lds = (size_t)NS * STEM_BM * 32 + (size_t)sh.NR * (W + 6) * 16;
     return sh;
 }
 
@@ -265,33 +251,13 @@ int launch_stem_f16(const SdcConvDesc& d, const float* x, const _Float16* wh, co
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wh) % 16 == 0, SDC_EALIGN, "sdc_conv_stem_f16: the packed weight buffer must be 16-byte aligned");
     const StemShape sh = stem_shape(d);
     // (every descriptor that stem_f16_ok covers stages at most 2048 positions in at most 91 KB of LDS)
-    SDC_REQUIRE(sh.itemsB <= 8 * SF_NT && sh.lds <= 160u * 1024u, SDC_EINVAL, "sdc_conv_stem_f16: staging of %d positions / %zu bytes of LDS",
+    SDC_REQUIRE(sh.itemsB <= 8 * STEM_NT && sh.lds <= 160u * 1024u, SDC_EINVAL, "sdc_conv_stem_f16: staging of %d positions / %zu bytes of LDS",
                 sh.itemsB, sh.lds);
     StemArgs a;
-    a.x = x; a.wh = wh; a.bias = bias; a.y = y;
-    for (int i = 0; i < 5; ++i) { a.xs[i] = d.x0s[i]; a.ys[i] = d.ys[i]; }
-    a.B = d.B; a.Cin = d.Cin0; a.Cout = d.Cout; a.oD = d.oD; a.oH = d.oH; a.W = d.oW;
-    a.lgW = d.oW == 16 ? 4 : d.oW == 32 ? 5 : d.oW == 64 ? 6 : 7;
-    a.kD = d.kD;
-    a.Hs = sh.Hs; a.NR = sh.NR;
-    const int64_t ntot = (int64_t)d.B * d.oD * d.oH * d.oW;
-    SDC_REQUIRE(ntot < (1ll << 31), SDC_EINVAL, "sdc_conv_stem_f16: too many output positions");
-    a.Ntot = (int)ntot;
-    a.ntiles = (a.Ntot + SF_BN - 1) / SF_BN; a.mtiles = d.Cout / SF_BM;
-    a.itemsB = sh.itemsB;
-    SDC_REQUIRE((int64_t)a.ntiles * a.mtiles < (1ll << 31), SDC_EINVAL, "sdc_conv_stem_f16: grid too large");
-    const dim3 grid((unsigned)(a.ntiles * a.mtiles));
-#define STEM_LAUNCH(KH, ITB)                                                                                        \
-    do {                                                                                                            \
-        static std::atomic<uint64_t> attr{0};                                                                       \
-        SDC_LDS_OPTIN(attr, (conv_stem_f16_kernel<KH, ITB>), 160 * 1024, "sdc_conv_stem_f16");                      \
-        hipLaunchKernelGGL((conv_stem_f16_kernel<KH, ITB>), grid, dim3(SF_NT), sh.lds, s, a);                       \
-    } while (0)
-    if (d.kH == 1) STEM_LAUNCH(1, 1);                           // (256 / W rows of W columns: one position per thread)
-    else if (sh.itemsB <= 2 * SF_NT) STEM_LAUNCH(7, 2);
-    else if (sh.itemsB <= 4 * SF_NT) STEM_LAUNCH(7, 4);
-    else STEM_LAUNCH(7, 8);
-#undef STEM_LAUNCH
+    a.wh = wh;
+    if (const int rc = stem_fill_args("sdc_conv_stem_f16", d, sh, x, bias, y, a)) return rc;
+    const size_t lds = sh.lds;
+    STEM_LAUNCH(conv_stem_f16_kernel, "sdc_conv_stem_f16");
     return sdc::check_launch("sdc_conv_stem_f16");
 }
 

@@ -11,7 +11,8 @@
 //
 // The walk is conv_stem_f16_kernel's (sdc_conv_stem_f16.hip): K layout (one octet of 8 channels per tap, two taps per 16-deep step, NS =
 // ceil(7 kH / 2) steps per kd plane), plane-group row staging with zero halo columns, the three fragment bases, the 64 x 256 tile with
-// four waves of 2 x 2 32x32 accumulators, the epilogue.  What differs:
+// four waves of 2 x 2 32x32 accumulators, the epilogue.  The tile geometry, the common arguments with their host fill, a workgroup's tile
+// and the launch ladder are sdc_conv_stem_tile.h's, the split and the term order sdc_split3.h's.  What differs:
 //   Weights: Wb[piece][kd][s][co][8 h + ci] bf16 (include/sdc.h, sdc_pack_stem_x3): three planes, each with the layout of sdc_pack_stem_f16.
 //   Activations: read as fp32 and split into three pieces while staged (v_cvt_pk_bf16_f32 and exact fp32 subtractions): three LDS images
 //     [slot row][col + 6][8] bf16, staged ONCE per kd plane.
@@ -22,27 +23,15 @@
 // Every stage runs for every tile (a clipped kd adds exact zeros), no K split, no atomics: a sample's bits never depend on its tile
 // mates or on the batch.  Epilogue: bias, fp32 stores through the descriptor's strides.
 #include "sdc_conv.h"
+#include "sdc_conv_stem_tile.h"
 #include "sdc_split3.h"
 
 using namespace sdcconv;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int SX_BM = 64, SX_BN = 256, SX_NT = 256;
-
 struct StemX3Args {
-    const float* x;
-    const __bf16* wb;
-    const float* bias;
-    float* y;
-    int64_t xs[5], ys[5];
-    int B, Cin, Cout, oD, oH, W, lgW;
-    int kD;
-    int Hs, NR;               // rows of a plane a tile can hold, staged slot rows (planes a tile can touch * (Hs + KH - 1))
-    int Ntot, ntiles, mtiles;
-    int itemsB;               // NR * W staged positions
+    STEM_TILE_ARGS(__bf16, wb)
     int plane;                // bf16 elements of one weight piece: kD * NS * Cout * 16
 };
 
@@ -53,28 +42,25 @@ struct StemX3Args {
 // the stem's rounding-order difference then showed in the C4 trajectory against the eager oracle.  With sm the main accumulator is
 // rounded once per step and sm's ulp is 2^-8 of it.  128 accumulator registers: one workgroup per CU.
 template <int KH, int ITB>
-__global__ __launch_bounds__(SX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_NO_DS_MERGE void conv_stem_x3_kernel(const StemX3Args a) {
+__global__ __launch_bounds__(STEM_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_NO_DS_MERGE void conv_stem_x3_kernel(const StemX3Args a) {
     constexpr int TAPS = KH * 7;
     constexpr int NS = (TAPS + 1) / 2;                          // 16-deep MFMA steps per kd plane
     constexpr int SS = KH == 7 ? 5 : NS;                        // steps per weight sub-stage
     constexpr int NSUB = NS / SS;
     static_assert(NSUB * SS == NS, "whole sub-stages");
     constexpr int HH = KH - 1;                                  // halo rows per plane group
-    constexpr int APC = SS * SX_BM * 32;                        // bytes of one piece of the A image
+    constexpr int APC = SS * STEM_BM * 32;                        // bytes of one piece of the A image
     constexpr int ASZ = 3 * APC;
-    constexpr int NIA = 3 * SS * SX_BM * 2;                     // 16-byte A items per sub-stage
-    constexpr int ITA = (NIA + SX_NT - 1) / SX_NT;
+    constexpr int NIA = 3 * SS * STEM_BM * 2;                     // 16-byte A items per sub-stage
+    constexpr int ITA = (NIA + STEM_NT - 1) / STEM_NT;
     extern __shared__ __attribute__((aligned(16))) char lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     const int W = a.W, RP = W + 6;                              // LDS row pitch in positions
     const int BIMG = a.NR * RP * 16;                            // bytes of one activation image
-    const int logical = xcd_tile(blockIdx.x, a.ntiles * a.mtiles);
-    const int mt = logical % a.mtiles, nt = logical / a.mtiles;
-    const int m0 = mt * SX_BM, n0 = nt * SX_BN;
-    const int r0 = n0 >> a.lgW;                                 // first row of the tile in the (b, od, oh) walk
-    const int plane0 = r0 / a.oH, oh0 = r0 - plane0 * a.oH;
+    const StemTile t = stem_tile(a);
+    const int m0 = t.m0, n0 = t.n0, r0 = t.r0, plane0 = t.plane0, oh0 = t.oh0;
     const int GR = a.Hs + HH;                                   // slot rows per plane group
 
     // ---- per-thread B staging items: (slot row sr, column w), w fastest; bases without the depth-tap part
@@ -83,7 +69,7 @@ __global__ __launch_bounds__(SX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
     bool bok[ITB];
 #pragma unroll
     for (int k = 0; k < ITB; ++k) {
-        const int it = tid + k * SX_NT;
+        const int it = tid + k * STEM_NT;
         const int w = it & (W - 1);
         const int sr = it >> a.lgW;
         int pl, ih;
@@ -100,9 +86,9 @@ __global__ __launch_bounds__(SX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
     int aoff[ITA];
 #pragma unroll
     for (int k = 0; k < ITA; ++k) {
-        const int it = tid + k * SX_NT;
-        const int p = it / (SS * 2 * SX_BM), q = it - p * (SS * 2 * SX_BM);
-        const int s = q / (2 * SX_BM), r = q - s * (2 * SX_BM);
+        const int it = tid + k * STEM_NT;
+        const int p = it / (SS * 2 * STEM_BM), q = it - p * (SS * 2 * STEM_BM);
+        const int s = q / (2 * STEM_BM), r = q - s * (2 * STEM_BM);
         aoff[k] = it < NIA ? p * a.plane + (s * a.Cout + m0) * 16 + r * 8 : 0;      // bf16 elements; + (kd * NS + sub * SS) * Cout * 16 per stage
     }
 
@@ -113,7 +99,7 @@ __global__ __launch_bounds__(SX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
 #pragma unroll
         for (int k = 0; k < ITA; ++k) {
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (tid + k * SX_NT < NIA) v = *reinterpret_cast<const uint4*>(a.wb + wst + aoff[k]);
+            if (tid + k * STEM_NT < NIA) v = *reinterpret_cast<const uint4*>(a.wb + wst + aoff[k]);
             av[k] = v;
         }
     };
@@ -131,15 +117,14 @@ __global__ __launch_bounds__(SX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
     auto store_a = [&]() {
 #pragma unroll
         for (int k = 0; k < ITA; ++k)
-            if (tid + k * SX_NT < NIA) *reinterpret_cast<uint4*>(lds + (tid + k * SX_NT) * 16) = av[k];
+            if (tid + k * STEM_NT < NIA) *reinterpret_cast<uint4*>(lds + (tid + k * STEM_NT) * 16) = av[k];
     };
     auto store_b = [&]() {
 #pragma unroll
         for (int k = 0; k < ITB; ++k) {
-            if (tid + k * SX_NT < a.itemsB) {
+            if (tid + k * STEM_NT < a.itemsB) {
                 bf16x8 h, m, l;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { __bf16 ph, pm, pl; split3(bv[k][i], ph, pm, pl); h[i] = ph; m[i] = pm; l[i] = pl; }
+                split3x8(bv[k], h, m, l);
                 *reinterpret_cast<bf16x8*>(lds + bdst[k]) = h;
                 *reinterpret_cast<bf16x8*>(lds + bdst[k] + BIMG) = m;
                 *reinterpret_cast<bf16x8*>(lds + bdst[k] + 2 * BIMG) = l;
@@ -148,7 +133,7 @@ __global__ __launch_bounds__(SX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
     };
 
     // zero halo columns 0..2 and W+3..W+5 of every slot row of the three images (never overwritten: the staged columns are 3..W+2)
-    for (int e = tid; e < 3 * a.NR * 6; e += SX_NT) {
+    for (int e = tid; e < 3 * a.NR * 6; e += STEM_NT) {
         const int sr = e / 6, c = e - sr * 6;                   // sr runs over the 3 * NR rows of the three images (BIMG = NR rows)
         *reinterpret_cast<uint4*>(lds + ASZ + (sr * RP + (c < 3 ? c : W + c)) * 16) = make_uint4(0u, 0u, 0u, 0u);
     }
@@ -209,15 +194,14 @@ __global__ __launch_bounds__(SX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
-                        af[i][p] = *reinterpret_cast<const bf16x8*>(lds + p * APC + (sl * SX_BM + 32 * i) * 32 + aoffr);
+                        af[i][p] = *reinterpret_cast<const bf16x8*>(lds + p * APC + (sl * STEM_BM + 32 * i) * 32 + aoffr);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int bs = (s == NS - 1) ? bC[j] : (kw == 6 ? bB[j] : bA[j]);
 #pragma unroll
                     for (int p = 0; p < 3; ++p) bf[j][p] = *reinterpret_cast<const bf16x8*>(lds + bs + tb + p * BIMG);
                 }
-                // smallest terms first: a3 b1, a2 b2, a1 b3, a2 b1, a1 b2, a1 b1; the four accumulators take each term in turn
-                constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+                // the six terms in sdc_split3.h's order (smallest first); the four accumulators take each term in turn
 #pragma unroll
                 for (int t = 0; t < 6; ++t)
 #pragma unroll
@@ -225,7 +209,7 @@ __global__ __launch_bounds__(SX_NT) __attribute__((amdgpu_waves_per_eu(1))) SDC_
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
                             f32x16& c = t < 5 ? sm[i][j] : acc[i][j];
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[t]], bf[j][PB[t]], c, 0, 0, 0);
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][X3_PA[t]], bf[j][X3_PB[t]], c, 0, 0, 0);
                         }
             }
         }
@@ -292,38 +276,17 @@ int launch_stem_x3(const SdcConvDesc& d, const float* x, const __bf16* wb, const
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wb) % 16 == 0, SDC_EALIGN, "sdc_conv_stem_x3: the packed weight buffer must be 16-byte aligned");
     const StemShape sh = stem_shape(d);
     const int NS = (d.kH * 7 + 1) / 2, SS = d.kH == 7 ? 5 : NS;
-    const size_t lds = (size_t)3 * SS * SX_BM * 32 + (size_t)3 * sh.NR * (d.oW + 6) * 16;
+    const size_t lds = (size_t)3 * SS * STEM_BM * 32 + (size_t)3 * sh.NR * (d.oW + 6) * 16;
     // (every descriptor that stem_f16_ok covers stages at most 2048 positions; three images of at most 40 KB and 30 KB of weights)
-    SDC_REQUIRE(sh.itemsB <= 8 * SX_NT && lds <= 160u * 1024u, SDC_EINVAL, "sdc_conv_stem_x3: staging of %d positions / %zu bytes of LDS",
+    SDC_REQUIRE(sh.itemsB <= 8 * STEM_NT && lds <= 160u * 1024u, SDC_EINVAL, "sdc_conv_stem_x3: staging of %d positions / %zu bytes of LDS",
                 sh.itemsB, lds);
     StemX3Args a;
-    a.x = x; a.wb = wb; a.bias = bias; a.y = y;
-    for (int i = 0; i < 5; ++i) { a.xs[i] = d.x0s[i]; a.ys[i] = d.ys[i]; }
-    a.B = d.B; a.Cin = d.Cin0; a.Cout = d.Cout; a.oD = d.oD; a.oH = d.oH; a.W = d.oW;
-    a.lgW = d.oW == 16 ? 4 : d.oW == 32 ? 5 : d.oW == 64 ? 6 : 7;
-    a.kD = d.kD;
-    a.Hs = sh.Hs; a.NR = sh.NR;
-    const int64_t ntot = (int64_t)d.B * d.oD * d.oH * d.oW;
-    SDC_REQUIRE(ntot < (1ll << 31), SDC_EINVAL, "sdc_conv_stem_x3: too many output positions");
+    a.wb = wb;
+    if (const int rc = stem_fill_args("sdc_conv_stem_x3", d, sh, x, bias, y, a)) return rc;
     const int64_t plane = (int64_t)d.kD * NS * d.Cout * 16;
     SDC_REQUIRE(3 * plane < (1ll << 31), SDC_EINVAL, "sdc_conv_stem_x3: weight too large");
     a.plane = (int)plane;
-    a.Ntot = (int)ntot;
-    a.ntiles = (a.Ntot + SX_BN - 1) / SX_BN; a.mtiles = d.Cout / SX_BM;
-    a.itemsB = sh.itemsB;
-    SDC_REQUIRE((int64_t)a.ntiles * a.mtiles < (1ll << 31), SDC_EINVAL, "sdc_conv_stem_x3: grid too large");
-    const dim3 grid((unsigned)(a.ntiles * a.mtiles));
-#define STEM_LAUNCH(KH, ITB)                                                                                        \
-    do {                                                                                                            \
-        static std::atomic<uint64_t> attr{0};                                                                       \
-        SDC_LDS_OPTIN(attr, (conv_stem_x3_kernel<KH, ITB>), 160 * 1024, "sdc_conv_stem_x3");                        \
-        hipLaunchKernelGGL((conv_stem_x3_kernel<KH, ITB>), grid, dim3(SX_NT), lds, s, a);                           \
-    } while (0)
-    if (d.kH == 1) STEM_LAUNCH(1, 1);                           // (256 / W rows of W columns: one position per thread)
-    else if (sh.itemsB <= 2 * SX_NT) STEM_LAUNCH(7, 2);
-    else if (sh.itemsB <= 4 * SX_NT) STEM_LAUNCH(7, 4);
-    else STEM_LAUNCH(7, 8);
-#undef STEM_LAUNCH
+    STEM_LAUNCH(conv_stem_x3_kernel, "sdc_conv_stem_x3");
     return sdc::check_launch("sdc_conv_stem_x3");
 }
 

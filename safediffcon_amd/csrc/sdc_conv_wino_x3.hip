@@ -33,7 +33,6 @@ using namespace sdcconv;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float w2f2 __attribute__((ext_vector_type(2)));
 typedef float nfloat4 __attribute__((ext_vector_type(4)));
@@ -437,12 +436,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void c
         constexpr bool first = decltype(FIRST)::value;
         constexpr int j = decltype(J)::value;
         constexpr int rbuf = j & 1, wbuf = rbuf ^ 1, jn = (j + 1) & 3;
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
         for (int sl = 0; sl < 24; ++sl) {
             const int xi = sl / 6, t = sl % 6, c = 4 * j + xi, set = xi & 1;
             const f32x16 cstart = (first && t == 0) ? ((c == 5 && pass == 0) ? biasv : zero16) : acc[c];
-            if (!(DBG & 64) || t == 0) acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[set][PA[t]], fr[set][3 + PB[t]], cstart, 0, 0, 0);
+            if (!(DBG & 64) || t == 0) acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[set][X3_PA[t]], fr[set][3 + X3_PB[t]], cstart, 0, 0, 0);
             if (DBG & 16) {}
             else if (xi < 3) read_frag(rbuf, xi + 1, set ^ 1, t);
             else if (t >= 3) { read_frag(wbuf, 0, 0, 2 * (t - 3)); read_frag(wbuf, 0, 0, 2 * (t - 3) + 1); }

@@ -26,10 +26,10 @@
 // No atomics, fixed accumulation order, a sample's arithmetic does not see the batch.
 #include "sdc_common.h"
 #include "sdc_lablock_tile.h"
+#include "sdc_f16frag.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 constexpr int TP = TT + 8;               // pitch (halves) of one channel row of the channel-major xn: 64 tokens + 16 bytes
 __host__ __device__ constexpr int cpitch(int C) { return C + 8; }      // pitch (halves) of one token of the token-major xn
 
@@ -54,14 +54,6 @@ struct La16Args {
 };
 
 __host__ __device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
-// registers r0 .. r0 + 7 of an accumulator, scaled and rounded to nearest even: one K fragment of the next product
-__device__ __forceinline__ half8 frag(const f32x16& acc, int r0, float scale = 1.0f) {
-    half8 h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (_Float16)(acc[r0 + j] * scale);
-    return h;
-}
 
 // 2^d for an integer-valued d <= 0 (-inf included): exact
 __device__ __forceinline__ float pow2_neg(float d) { return ldexpf(1.0f, (int)fmaxf(d, -200.0f)); }

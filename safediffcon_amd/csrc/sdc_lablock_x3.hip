@@ -22,7 +22,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 __host__ __device__ constexpr int cpitch(int C) { return C + 8; }      // pitch (bf16) of one token of a piece image: C channels + 16 bytes
 // xn pieces whose fragments a wave keeps in registers across the six terms at C = 64 (project_x3): pass 1 has room for all three,
 // pass 2 (64 registers of T) for the first
@@ -93,12 +92,7 @@ __device__ __forceinline__ void norm_tile_x3(float (&v)[C / 4], const float* __r
 #pragma unroll
     for (int c8 = 0; c8 < CG / 8; ++c8) {
         bf16x8 ph, pm, pl;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            __bf16 h, m, l;
-            split3(o[c8 * 8 + j], h, m, l);
-            ph[j] = h; pm[j] = m; pl[j] = l;
-        }
+        split3x8(o + c8 * 8, ph, pm, pl);
         xo[c8] = ph;
         xo[piece_e(C) / 8 + c8] = pm;
         xo[2 * (piece_e(C) / 8) + c8] = pl;
@@ -113,7 +107,7 @@ __device__ __forceinline__ void split_weight(const float* __restrict__ wqkv, int
 #pragma unroll
     for (int s = 0; s < C / 16; ++s)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < 8; ++j) {       // (open-coded: through split3x8 and a staging array la_x3_out<128> compiles to other instructions)
             __bf16 h, m, l;
             split3(wqkv[(int64_t)(16 * s + 8 * lh + j) * (3 * HID) + col], h, m, l);
             w[0][s][j] = h; w[1][s][j] = m; w[2][s][j] = l;
@@ -126,8 +120,7 @@ __device__ __forceinline__ void split_weight(const float* __restrict__ wqkv, int
 template <int C, bool XA, int NPRE>
 __device__ __forceinline__ void project_x3(const bf16x8 (&w)[3][C / 16], const __bf16* __restrict__ xt, int l31, int lh, f32x16 (&acc)[2]) {
     constexpr int NKS = C / 16, CP8 = cpitch(C) / 8, PE8 = piece_e(C) / 8;
-    // the six terms, smallest kind first: weight piece PA[t] with xn piece PB[t]
-    constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+    // the six terms in sdc_split3.h's order: weight piece X3_PA[t] with xn piece X3_PB[t]
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
     const bf16x8* xp = reinterpret_cast<const bf16x8*>(xt) + l31 * CP8 + lh;
@@ -146,9 +139,9 @@ __device__ __forceinline__ void project_x3(const bf16x8 (&w)[3][C / 16], const _
         for (int s = 0; s < NKS; ++s)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const bf16x8 xv = PB[t] < NPRE ? xf[PB[t] < NPRE ? PB[t] : 0][j][s] : xp[PB[t] * PE8 + j * 32 * CP8 + 2 * s];
-                acc[j] = XA ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(xv, w[PA[t]][s], acc[j], 0, 0, 0)
-                            : __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[PA[t]][s], xv, acc[j], 0, 0, 0);
+                const bf16x8 xv = X3_PB[t] < NPRE ? xf[X3_PB[t] < NPRE ? X3_PB[t] : 0][j][s] : xp[X3_PB[t] * PE8 + j * 32 * CP8 + 2 * s];
+                acc[j] = XA ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(xv, w[X3_PA[t]][s], acc[j], 0, 0, 0)
+                            : __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[X3_PA[t]][s], xv, acc[j], 0, 0, 0);
             }
         // (C = 64, two waves per SIMD: a term's fragment reads stay with the term -- hoisted, they spill; C = 128 has the registers)
         if (C == 64 && NPRE < 3) __builtin_amdgcn_sched_barrier(0);

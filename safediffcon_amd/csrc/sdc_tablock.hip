@@ -18,48 +18,14 @@
 // x is read twice (the second time for the residual, L2/MALL-warm), y written once.  fp32 MFMA throughout.
 // Workgroups are persistent (one per CU) and walk the pixel groups: tables staged once, the next group's x and head 0's
 // weights requested while the current group is on the matrix cores.
-#include "sdc_common.h"
-#include <cstdlib>
+// The arguments, the tile geometry, the wave-uniform-base accessors, the walk and the entries' common checks live in sdc_tablock_tile.h,
+// shared with the fp16-operand and bf16-split variants of this kernel.
+#define TA_WEIGHT_ARGS const float* wqkv; const float* wo;
+#include "sdc_tablock_tile.h"
 
 namespace {
 
-constexpr int NT = 512;                  // 8 waves: one pixel each, two waves per SIMD
-constexpr int C = 64;
-constexpr int NS = 8;                    // pixels per workgroup
-constexpr int XP = NS * 33;              // LDS pitch of one channel row: [pixel][33 frames]
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct TaArgs {
-    const float* x; const float* g; const float* wqkv; const float* wo; const float* rot; const float* bias;
-    float* y;
-    int inner;               // pixels per outer index (H*W)
-    int nblk;                // pixel groups of NS
-    float eps;
-    int64_t so, sc, st;      // element (o, c, pixel i, frame f) at o*so + c*sc + f*st + i
-#ifdef SDC_KERNEL_EXPERIMENTS
-    int dbg;                 // kernel experiments (SDC_TA_DBG; WRONG RESULTS): 1 no head loop, 2 no weight fetches, 4 no softmax / rotary
-#define TA_DBG(a) ((a).dbg)
-#else
-#define TA_DBG(a) 0         // the shipping library has no result-changing switches (build with -DSDC_KERNEL_EXPERIMENTS for them)
-#endif
-};
-
-__device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
-// wave-uniform base (SGPR pair) + 32-bit per-lane byte offset: `global_load_dword v, v_off, s[base:base+1]` -- one VGPR of
-// address for all 32 channel rows of a token instead of a 64-bit pointer per row
-typedef __attribute__((address_space(1))) float* gptr_t;
-typedef __attribute__((address_space(1))) char* gcptr_t;
-__device__ __forceinline__ gptr_t uni(const float* p) {
-    const uint64_t u = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-    return (gptr_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ float ldu(gptr_t base, uint32_t byte_off) { return *(gptr_t)((gcptr_t)base + byte_off); }
-__device__ __forceinline__ void stu(gptr_t base, uint32_t byte_off, float v) { *(gptr_t)((gcptr_t)base + byte_off) = v; }
-
 // packed rotary step: x = (x0, x1), cs = (cos, sin) -> (x0 cos - x1 sin, x1 cos + x0 sin) in two VALU instructions
-typedef float ta2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ ta2 ta_rot(ta2 x, ta2 cs) {
     ta2 t, r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(x), "v"(cs));                       // (x0 c, x1 c)
@@ -76,26 +42,15 @@ __global__ __launch_bounds__(NT) void ta_block_kernel(const TaArgs a) {
     float* const wl = red + 1024;                 // [2][8192] weights of one head: Wq | Wk | Wv ([64 c][32 d] each) | Wo ([32 d][64 co])
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    // Persistent workgroups (one per CU): the bias / rotary tables are staged once, head 0's weights and the x tile of the
+    // Persistent workgroups (one per CU; ta_walk): the bias / rotary tables are staged once, head 0's weights and the x tile of the
     // NEXT pixel group travel while the current one is on the matrix cores, so a tile's only exposed memory latency is the
-    // first one's.  XCD-aware walk: workgroup w runs on XCD w & 7 (round-robin dispatch); each XCD takes a contiguous
-    // eighth of the pixel groups and its workgroups interleave over it, so the 4 groups sharing a 128-byte line are in
-    // flight on one XCD at about the same time (speed only).
-    const int nblk = a.nblk, nwg = gridDim.x, w = blockIdx.x;
-    const bool xcd = ((nblk & 7) == 0) && ((nwg & 7) == 0);
-    const int per = xcd ? (nblk >> 3) : nblk;             // tiles of this workgroup's share
-    const int base = xcd ? (w & 7) * per : 0;
-    const int first = xcd ? (w >> 3) : w, stride = xcd ? (nwg >> 3) : nwg;
-    typedef float nfloat4 __attribute__((ext_vector_type(4)));
+    // first one's.
+    const TaWalk wk = ta_walk(a.nblk);
+    const int per = wk.per, first = wk.first, stride = wk.stride;
 
     const int tok = tid & 255, half = tid >> 8, pw = tok & 7, f = tok >> 3;
     const uint32_t toff = (uint32_t)(((int64_t)f * a.st + pw + (int64_t)(half * 32) * a.sc) * 4);   // this thread's token (byte
                                                    // offset inside one outer index: < 2^32, host check); 32 channels from here
-    auto tile_ptr = [&](int li) -> int64_t {
-        const int seq0 = (base + li) * NS;
-        const int o = seq0 / a.inner, i0 = seq0 - o * a.inner;
-        return (int64_t)o * a.so + i0;
-    };
 
     // ---- once per workgroup: head 0's weights, the transposed bias table, the rotary table
     nfloat4 wreg[4];
@@ -119,7 +74,7 @@ __global__ __launch_bounds__(NT) void ta_block_kernel(const TaArgs a) {
     };
     float v[32];                                   // raw x of the tile about to be normalised (this thread's token, 32 channels)
     if (first < per) {
-        const float* xt = a.x + tile_ptr(first);
+        const float* xt = a.x + ta_tile_ptr(a, wk, first);
 #pragma unroll
         for (int c = 0; c < 32; ++c) v[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
     }
@@ -173,7 +128,7 @@ __global__ __launch_bounds__(NT) void ta_block_kernel(const TaArgs a) {
     };
 
     for (int li = first; li < per; li += stride) {
-        const int64_t tp = tile_ptr(li);
+        const int64_t tp = ta_tile_ptr(a, wk, li);
         const bool more = li + stride < per;
         // ---- 1. LayerNorm over the 64 channels of a token (pixel pw, frame f): two threads per token, 32 channels each
         {
@@ -266,7 +221,7 @@ __global__ __launch_bounds__(NT) void ta_block_kernel(const TaArgs a) {
             for (int c = 0; c < 32; ++c) xr[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
         }
         {   // (unconditional: a conditional load would keep the old v alive across the whole head loop; the last tile re-reads itself)
-            const float* xt = a.x + tile_ptr(more ? li + stride : li);
+            const float* xt = a.x + ta_tile_ptr(a, wk, more ? li + stride : li);
 #pragma unroll
             for (int c = 0; c < 32; ++c) v[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
         }
@@ -287,23 +242,30 @@ __global__ __launch_bounds__(NT) void ta_block_kernel(const TaArgs a) {
 
 }  // namespace
 
+// (sdc_tablock_tile.h)  The CU count of a device is queried once, like the LDS opt-in: no runtime query per launch, no guessed grid.
+int sdc::ta_grid(const char* entry, int64_t nblk, unsigned* grid) {
+    static std::atomic<int> ncu_of[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { sdc::set_error("%s: hipGetDevice failed", entry); return SDC_EHIP; }
+    int ncu = ncu_of[dev].load(std::memory_order_acquire);
+    if (ncu <= 0) {
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
+            sdc::set_error("%s: cannot read the CU count of device %d", entry, dev);
+            return SDC_EHIP;
+        }
+        ncu_of[dev].store(ncu, std::memory_order_release);
+    }
+    *grid = (unsigned)(nblk < ncu ? nblk : ncu);
+    return SDC_OK;
+}
+
 extern "C" int sdc_tattn_block(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* rot,
                                const float* bias, float* y, int outer, int inner, int Cc, int ntok, int64_t so, int64_t sc,
                                int64_t st, float eps, void* stream) {
-    SDC_REQUIRE(x && g_pre && wqkv && wo && y, SDC_ENULL, "sdc_tattn_block: null pointer");
-    SDC_REQUIRE(Cc == 64 && ntok == 32, SDC_EINVAL, "sdc_tattn_block: dim 64 and 32 frames only (got %d, %d)", Cc, ntok);
-    SDC_REQUIRE(outer > 0 && inner > 0 && inner % NS == 0, SDC_EINVAL, "sdc_tattn_block: pixels per image must be a multiple of 8");
-    const int64_t nblk = (int64_t)outer * inner / NS;
-    SDC_REQUIRE(nblk < (1ll << 31), SDC_EINVAL, "sdc_tattn_block: too many sequences");
-    SDC_REQUIRE(((int64_t)31 * st + inner + (int64_t)63 * sc) * 4 < (1ll << 32) && so >= 0 && sc >= 0 && st >= 0, SDC_EINVAL,
-                "sdc_tattn_block: one outer index must span less than 4 GB (32-bit lane offsets)");
+    SDC_REQUIRE(wqkv && wo, SDC_ENULL, "sdc_tattn_block: null pointer");
     TaArgs a;
-    a.x = x; a.g = g_pre; a.wqkv = wqkv; a.wo = wo; a.rot = rot; a.bias = bias; a.y = y;
-    a.inner = inner; a.nblk = (int)nblk; a.eps = eps; a.so = so; a.sc = sc; a.st = st;
-#ifdef SDC_KERNEL_EXPERIMENTS
-    static const int dbg = getenv("SDC_TA_DBG") ? atoi(getenv("SDC_TA_DBG")) : 0;
-    a.dbg = dbg;
-#endif
+    if (const int rc = ta_check_args("sdc_tattn_block", x, g_pre, rot, bias, y, outer, inner, Cc, ntok, so, sc, st, eps, a)) return rc;
+    a.wqkv = wqkv; a.wo = wo;
     // the prologue reads the weights with 16-byte and the rotary table with 8-byte vector loads
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wqkv) % 16 == 0 && reinterpret_cast<uintptr_t>(wo) % 16 == 0 &&
                 (!rot || reinterpret_cast<uintptr_t>(rot) % 8 == 0), SDC_EINVAL,
@@ -311,20 +273,8 @@ extern "C" int sdc_tattn_block(const float* x, const float* g_pre, const float* 
     const size_t ldsb = sizeof(float) * (size_t)(C * XP + 4 * 32 * 33 + 2 * 32 * 16 + 1024 + 2 * 8192);
     static std::atomic<uint64_t> attr{0};
     SDC_LDS_OPTIN(attr, ta_block_kernel, 160 * 1024, "sdc_tattn_block");
-    // one persistent workgroup per CU (157 KB of LDS: one fits), at most one per pixel group
-    // (the CU count of a device is queried once, like the LDS opt-in: no runtime query per launch, no guessed grid)
-    static std::atomic<int> ncu_of[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { sdc::set_error("sdc_tattn_block: hipGetDevice failed"); return SDC_EHIP; }
-    int ncu = ncu_of[dev].load(std::memory_order_acquire);
-    if (ncu <= 0) {
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
-            sdc::set_error("sdc_tattn_block: cannot read the CU count of device %d", dev);
-            return SDC_EHIP;
-        }
-        ncu_of[dev].store(ncu, std::memory_order_release);
-    }
-    const unsigned grid = (unsigned)(nblk < ncu ? nblk : ncu);
+    unsigned grid = 0;
+    if (const int rc = sdc::ta_grid("sdc_tattn_block", a.nblk, &grid)) return rc;
     hipLaunchKernelGGL(ta_block_kernel, dim3(grid), dim3(NT), ldsb, sdc::as_stream(stream), a);
     return sdc::check_launch("sdc_tattn_block");
 }

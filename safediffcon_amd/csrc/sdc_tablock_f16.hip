@@ -4,7 +4,8 @@
 //   y = x + Wo . softmax( rot(s Wq xn) rot(Wk xn)^T + relpos ) (Wv xn),   xn = channel LayerNorm(x) * gamma
 //
 // Same computation, tensor strides, tables and workgroup walk as ta_block_kernel (one persistent workgroup per CU, 8 adjacent
-// pixels per tile, one wave per pixel, all 32 frames, all 4 heads).  What differs:
+// pixels per tile, one wave per pixel, all 32 frames, all 4 heads); the arguments, the tile geometry, the wave-uniform-base accessors,
+// the walk and the entry's common checks are sdc_tablock_tile.h's, the fragment type and frag() sdc_f16frag.h's.  What differs:
 //   - per head and wave 12 + 2 + 2 + 4 = 20 MFMAs of K = 16 instead of 160 of K = 2;
 //   - xn is kept in LDS as fp16, [pixel][frame][channel]: the 8 channels of a lane's K fragment are one 16-byte read, and the four
 //     fragments of a wave's pixel are read once per tile and serve all four heads (as B operand of q and k, as A operand of V^T);
@@ -18,50 +19,15 @@
 // Rounded once to fp16 (RNE) as operands: xn, the weights (at pack time), q and k after the rotary (unscaled: the scale rides on the
 // softmax exponent), v, the un-normalised probabilities exp(s - max) in (0, 1], O after the division by the fp32 row sum.
 // No atomics, fixed accumulation order, a sample's arithmetic does not see the batch.
-#include "sdc_common.h"
+#define TA_WEIGHT_ARGS const _Float16* wpk;
+#include "sdc_tablock_tile.h"
+#include "sdc_f16frag.h"
 
 namespace {
 
-constexpr int NT = 512;                  // 8 waves: one pixel each, two waves per SIMD
-constexpr int C = 64;
-constexpr int NS = 8;                    // pixels per workgroup
-constexpr int XP = NS * 33;              // pitch of one channel row of the y image: [pixel][33 frames]
 constexpr int CP = 72;                   // pitch (halves) of one token of xn: 64 channels + 16 bytes
 constexpr int WQKV_H = 4 * 3 * 4 * 64 * 8;   // halves of the q / k / v fragments
 constexpr int WPK_H = WQKV_H + 4 * 2 * 2 * 64 * 8;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-struct TaArgs {
-    const float* x; const float* g; const _Float16* wpk; const float* rot; const float* bias;
-    float* y;
-    int inner;               // pixels per outer index (H*W)
-    int nblk;                // pixel groups of NS
-    float eps;
-    int64_t so, sc, st;      // element (o, c, pixel i, frame f) at o*so + c*sc + f*st + i
-};
-
-__host__ __device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
-// wave-uniform base (SGPR pair) + 32-bit per-lane byte offset, as in ta_block_kernel
-typedef __attribute__((address_space(1))) float* gptr_t;
-typedef __attribute__((address_space(1))) char* gcptr_t;
-__device__ __forceinline__ gptr_t uni(const float* p) {
-    const uint64_t u = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-    return (gptr_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ float ldu(gptr_t base, uint32_t byte_off) { return *(gptr_t)((gcptr_t)base + byte_off); }
-__device__ __forceinline__ void stu(gptr_t base, uint32_t byte_off, float v) { *(gptr_t)((gcptr_t)base + byte_off) = v; }
-
-// registers r0 .. r0 + 7 of an accumulator, scaled and rounded to nearest even: one K fragment of the next product
-__device__ __forceinline__ half8 frag(const f32x16& acc, int r0, float scale = 1.0f) {
-    half8 h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (_Float16)(acc[r0 + j] * scale);
-    return h;
-}
 
 __global__ __launch_bounds__(NT) void ta_block_f16_kernel(const TaArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_f16[];
@@ -73,25 +39,16 @@ __global__ __launch_bounds__(NT) void ta_block_f16_kernel(const TaArgs a) {
     float* const red = rotcs + 2 * 32 * 16;                             // [2][2][256] LayerNorm partials
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    // the walk of ta_block_kernel: workgroup w runs on XCD w & 7; each XCD takes a contiguous eighth of the pixel groups
-    const int nblk = a.nblk, nwg = gridDim.x, w = blockIdx.x;
-    const bool xcd = ((nblk & 7) == 0) && ((nwg & 7) == 0);
-    const int per = xcd ? (nblk >> 3) : nblk;
-    const int base = xcd ? (w & 7) * per : 0;
-    const int first = xcd ? (w >> 3) : w, stride = xcd ? (nwg >> 3) : nwg;
+    const TaWalk wk = ta_walk(a.nblk);
+    const int per = wk.per, first = wk.first, stride = wk.stride;
 
     const int tok = tid & 255, half = tid >> 8, pw = tok & 7, f = tok >> 3;
     const uint32_t toff = (uint32_t)(((int64_t)f * a.st + pw) * 4);     // this thread's token (byte offset inside one channel of one
                                                                         // outer index: < 2^32, host check)
-    auto tile_ptr = [&](int li) -> int64_t {
-        const int seq0 = (base + li) * NS;
-        const int o = seq0 / a.inner, i0 = seq0 - o * a.inner;
-        return (int64_t)o * a.so + i0;
-    };
 
     float v[32];                                   // raw x of the tile about to be normalised (this thread's token, channels half*32 ..)
     if (first < per) {
-        const float* xt = a.x + tile_ptr(first) + (int64_t)(half * 32) * a.sc;
+        const float* xt = a.x + ta_tile_ptr(a, wk, first) + (int64_t)(half * 32) * a.sc;
 #pragma unroll
         for (int c = 0; c < 32; ++c) v[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
     }
@@ -113,7 +70,7 @@ __global__ __launch_bounds__(NT) void ta_block_f16_kernel(const TaArgs a) {
     const int hw = wave;                           // this wave's pixel of the tile
 
     for (int li = first; li < per; li += stride) {
-        const int64_t tp = tile_ptr(li);
+        const int64_t tp = ta_tile_ptr(a, wk, li);
         const bool more = li + stride < per;
         // ---- 1. LayerNorm over the 64 channels of a token (pixel pw, frame f): two threads per token, 32 channels each; fp32, then
         //         one rounding to fp16
@@ -210,7 +167,7 @@ __global__ __launch_bounds__(NT) void ta_block_f16_kernel(const TaArgs a) {
         // ---- 3. the next tile's x is requested, then y leaves in two halves of 32 channels through the LDS space of xn: thread
         //         (token, half) adds the residual (L2-warm second read of x) to channels i*32 + half*16 .. + 16 and stores them
         {   // (unconditional: the last tile re-reads itself)
-            const float* xt = a.x + tile_ptr(more ? li + stride : li) + (int64_t)(half * 32) * a.sc;
+            const float* xt = a.x + ta_tile_ptr(a, wk, more ? li + stride : li) + (int64_t)(half * 32) * a.sc;
 #pragma unroll
             for (int c = 0; c < 32; ++c) v[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
         }
@@ -262,35 +219,18 @@ extern "C" int sdc_pack_tattn_f16(const float* wqkv, const float* wo, void* dst,
 
 extern "C" int sdc_tattn_block_f16(const float* x, const float* g_pre, const void* wpk, const float* rot, const float* bias, float* y,
                                    int outer, int inner, int Cc, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream) {
-    SDC_REQUIRE(x && g_pre && wpk && y, SDC_ENULL, "sdc_tattn_block_f16: null pointer");
-    SDC_REQUIRE(Cc == 64 && ntok == 32, SDC_EINVAL, "sdc_tattn_block_f16: dim 64 and 32 frames only (got %d, %d)", Cc, ntok);
-    SDC_REQUIRE(outer > 0 && inner > 0 && inner % NS == 0, SDC_EINVAL, "sdc_tattn_block_f16: pixels per image must be a multiple of 8");
-    const int64_t nblk = (int64_t)outer * inner / NS;
-    SDC_REQUIRE(nblk < (1ll << 31), SDC_EINVAL, "sdc_tattn_block_f16: too many sequences");
-    SDC_REQUIRE(((int64_t)31 * st + inner + (int64_t)63 * sc) * 4 < (1ll << 32) && so >= 0 && sc >= 0 && st >= 0, SDC_EINVAL,
-                "sdc_tattn_block_f16: one outer index must span less than 4 GB (32-bit lane offsets)");
+    SDC_REQUIRE(wpk, SDC_ENULL, "sdc_tattn_block_f16: null pointer");
+    TaArgs a;
+    if (const int rc = ta_check_args("sdc_tattn_block_f16", x, g_pre, rot, bias, y, outer, inner, Cc, ntok, so, sc, st, eps, a)) return rc;
+    a.wpk = reinterpret_cast<const _Float16*>(wpk);
     // the prologue copies the weight buffer with 16-byte and reads the rotary table with 8-byte vector loads
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wpk) % 16 == 0, SDC_EALIGN, "sdc_tattn_block_f16: the weight buffer must be 16-byte aligned");
     SDC_REQUIRE(!rot || reinterpret_cast<uintptr_t>(rot) % 8 == 0, SDC_EINVAL, "sdc_tattn_block_f16: rot must be 8-byte aligned");
-    TaArgs a;
-    a.x = x; a.g = g_pre; a.wpk = reinterpret_cast<const _Float16*>(wpk); a.rot = rot; a.bias = bias; a.y = y;
-    a.inner = inner; a.nblk = (int)nblk; a.eps = eps; a.so = so; a.sc = sc; a.st = st;
     const size_t ldsb = sizeof(_Float16) * (size_t)(WPK_H + NS * 32 * CP) + sizeof(float) * (size_t)(4 * 32 * 33 + 2 * 32 * 16 + 1024);
     static std::atomic<uint64_t> attr{0};
     SDC_LDS_OPTIN(attr, ta_block_f16_kernel, 160 * 1024, "sdc_tattn_block_f16");
-    // one persistent workgroup per CU (125 KB of LDS: one fits), at most one per pixel group; the CU count is queried once per device
-    static std::atomic<int> ncu_of[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { sdc::set_error("sdc_tattn_block_f16: hipGetDevice failed"); return SDC_EHIP; }
-    int ncu = ncu_of[dev].load(std::memory_order_acquire);
-    if (ncu <= 0) {
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
-            sdc::set_error("sdc_tattn_block_f16: cannot read the CU count of device %d", dev);
-            return SDC_EHIP;
-        }
-        ncu_of[dev].store(ncu, std::memory_order_release);
-    }
-    const unsigned grid = (unsigned)(nblk < ncu ? nblk : ncu);
+    unsigned grid = 0;
+    if (const int rc = sdc::ta_grid("sdc_tattn_block_f16", a.nblk, &grid)) return rc;
     hipLaunchKernelGGL(ta_block_f16_kernel, dim3(grid), dim3(NT), ldsb, sdc::as_stream(stream), a);
     return sdc::check_launch("sdc_tattn_block_f16");
 }

@@ -8,7 +8,8 @@
 //
 // An fp32-grade result in another rounding order, not a reduced precision.  Walk, tables and exit are ta_block_f16_kernel's (one
 // persistent workgroup per CU, 8 adjacent pixels per tile, one wave per pixel, all 32 frames, all 4 heads, XCD-ordered walk, the next
-// tile's x requested behind the head loop, y out through LDS in two halves).  What is split:
+// tile's x requested behind the head loop, y out through LDS in two halves); the arguments, the tile geometry, the wave-uniform-base
+// accessors, the walk and the entry's common checks are sdc_tablock_tile.h's, the split and the term order sdc_split3.h's.  What is split:
 //   - the weights, once, at pack time (sdc_pack_tattn_x3: three planes in sdc_pack_tattn_f16's fragment order, head by head);
 //   - xn, once per value and tile: the LayerNorm leaves an fp32 image [pixel][frame][channel] in LDS, every wave reads the 32 values of
 //     its lanes' fragments (frame l31, channels 16 s + 8 lh + j) and keeps their three pieces in registers (3 x 16 VGPRs) for all four
@@ -24,15 +25,12 @@
 // head h is on the matrix cores; head 3 brings head 0 of the next tile.  One barrier per head.
 // No atomics, fixed accumulation order, a sample's arithmetic does not see the batch.  A non-finite x gives NaN (inf - inf in the
 // residual of the split) where the fp32 kernel may give an infinity.
-#include "sdc_common.h"
+#define TA_WEIGHT_ARGS const __bf16* wpk;
+#include "sdc_tablock_tile.h"
 #include "sdc_split3.h"
 
 namespace {
 
-constexpr int NT = 512;                  // 8 waves: one pixel each, two waves per SIMD
-constexpr int C = 64;
-constexpr int NS = 8;                    // pixels per workgroup
-constexpr int XP = NS * 33;              // pitch of one channel row of the y image: [pixel][33 frames]
 constexpr int XF = 68;                   // pitch (floats) of one token of the xn image: 64 channels + 16 bytes
 constexpr int XPP = 32 * XF + 8;         // pitch (floats) of one pixel of the xn image (+ 32 bytes: the LayerNorm's stores spread over the banks)
 constexpr int WQKV_E = 3 * 4 * 64 * 8;   // bf16 elements of one head's q / k / v fragments (one piece)
@@ -40,38 +38,11 @@ constexpr int HEAD_E = WQKV_E + 2 * 2 * 64 * 8;      // ... of one head (one pie
 constexpr int WPK_E = 4 * 3 * HEAD_E;    // the whole buffer: [head][piece][HEAD_E]
 constexpr int WBUF_B = 3 * HEAD_E * 2;   // bytes of one head's weights: 49152
 constexpr int REGB_B = NS * XPP * 4;     // bytes of region B: 69888
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float nfloat4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 static_assert(WBUF_B <= REGB_B && 32 * XP * 4 <= REGB_B, "region B holds a head's weights and a y half");
 static_assert(WBUF_B % (16 * NT) == 0, "whole 16-byte words per thread");
 
-struct TaArgs {
-    const float* x; const float* g; const __bf16* wpk; const float* rot; const float* bias;
-    float* y;
-    int inner;               // pixels per outer index (H*W)
-    int nblk;                // pixel groups of NS
-    float eps;
-    int64_t so, sc, st;      // element (o, c, pixel i, frame f) at o*so + c*sc + f*st + i
-};
-
-__host__ __device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
-// wave-uniform base (SGPR pair) + 32-bit per-lane byte offset, as in ta_block_kernel
-typedef __attribute__((address_space(1))) float* gptr_t;
-typedef __attribute__((address_space(1))) char* gcptr_t;
-__device__ __forceinline__ gptr_t uni(const float* p) {
-    const uint64_t u = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-    return (gptr_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ float ldu(gptr_t base, uint32_t byte_off) { return *(gptr_t)((gcptr_t)base + byte_off); }
-__device__ __forceinline__ void stu(gptr_t base, uint32_t byte_off, float v) { *(gptr_t)((gcptr_t)base + byte_off) = v; }
-
 // rotary step: x = (x0, x1), cs = (cos, sin) -> (x0 cos - x1 sin, x1 cos + x0 sin) with the roundings of ta_block_kernel's packed pair
 // (a rounded product with the cosine, then one fused multiply-add with the sine), left to the compiler's instruction selection
-typedef float ta2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ ta2 ta_rot(ta2 x, ta2 cs) {
 #pragma clang fp contract(off)
     const float t0 = x.x * cs.x, t1 = x.y * cs.x;
@@ -89,21 +60,12 @@ __global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {
     float* const red = rotcs + 2 * 32 * 16;                             // [2][2][256] LayerNorm partials
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    // the walk of ta_block_kernel: workgroup w runs on XCD w & 7; each XCD takes a contiguous eighth of the pixel groups
-    const int nblk = a.nblk, nwg = gridDim.x, w = blockIdx.x;
-    const bool xcd = ((nblk & 7) == 0) && ((nwg & 7) == 0);
-    const int per = xcd ? (nblk >> 3) : nblk;
-    const int base = xcd ? (w & 7) * per : 0;
-    const int first = xcd ? (w >> 3) : w, stride = xcd ? (nwg >> 3) : nwg;
+    const TaWalk wk = ta_walk(a.nblk);
+    const int per = wk.per, first = wk.first, stride = wk.stride;
 
     const int tok = tid & 255, half = tid >> 8, pw = tok & 7, f = tok >> 3;
     const uint32_t toff = (uint32_t)(((int64_t)f * a.st + pw) * 4);     // this thread's token (byte offset inside one channel of one
                                                                         // outer index: < 2^32, host check)
-    auto tile_ptr = [&](int li) -> int64_t {
-        const int seq0 = (base + li) * NS;
-        const int o = seq0 / a.inner, i0 = seq0 - o * a.inner;
-        return (int64_t)o * a.so + i0;
-    };
 
     // one head's weights (three pieces, one contiguous run of 48 KB): six 16-byte words per thread, through registers
     u32x4 wreg[6];
@@ -120,7 +82,7 @@ __global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {
 
     float v[32];                                   // raw x of the tile about to be normalised (this thread's token, channels half*32 ..)
     if (first < per) {
-        const float* xt = a.x + tile_ptr(first) + (int64_t)(half * 32) * a.sc;
+        const float* xt = a.x + ta_tile_ptr(a, wk, first) + (int64_t)(half * 32) * a.sc;
 #pragma unroll
         for (int c = 0; c < 32; ++c) v[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
     }
@@ -140,7 +102,7 @@ __global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {
     const int hw = wave;                           // this wave's pixel of the tile
 
     for (int li = first; li < per; li += stride) {
-        const int64_t tp = tile_ptr(li);
+        const int64_t tp = ta_tile_ptr(a, wk, li);
         const bool more = li + stride < per;
         // ---- 1. LayerNorm over the 64 channels of a token (pixel pw, frame f): two threads per token, 32 channels each (fp32, the
         //         values of ta_block_kernel)
@@ -175,12 +137,8 @@ __global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const nfloat4 lo = *reinterpret_cast<const nfloat4*>(xr + 16 * s), hi = *reinterpret_cast<const nfloat4*>(xr + 16 * s + 4);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    __bf16 ph, pm, pl;
-                    split3(j < 4 ? lo[j] : hi[j - 4], ph, pm, pl);
-                    xf[0][s][j] = ph; xf[1][s][j] = pm; xf[2][s][j] = pl;
-                }
+                const float xv[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                split3x8(xv, xf[0][s], xf[1][s], xf[2][s]);
             }
         }
         f32x16 yacc[2];                                // row tiles of y (32 channels each)
@@ -190,8 +148,7 @@ __global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {
             for (int r = 0; r < 16; ++r) yacc[i][r] = 0.f;
 #pragma unroll 1
         for (int head = 0; head < 4; ++head) {
-            // the six terms of a product, smallest kind first: weight piece PA[t] with xn / O piece PB[t]
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+            // the six terms of a product in sdc_split3.h's order: weight piece X3_PA[t] with xn / O piece X3_PB[t]
             const unsigned char* const wh = (head & 1) ? rB : wA;
             unsigned char* const wn = (head & 1) ? wA : rB;
             __syncthreads();                           // this head's weights are in LDS; every wave is done with the other buffer (head 0:
@@ -208,10 +165,10 @@ __global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {
             for (int t = 0; t < 6; ++t)
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    const bf16x8* wp = wf + PA[t] * (HEAD_E / 8);
-                    q = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(0 * 4 + s) * 64], xf[PB[t]][s], q, 0, 0, 0);
-                    k = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(1 * 4 + s) * 64], xf[PB[t]][s], k, 0, 0, 0);
-                    vt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[PB[t]][s], wp[(2 * 4 + s) * 64], vt, 0, 0, 0);
+                    const bf16x8* wp = wf + X3_PA[t] * (HEAD_E / 8);
+                    q = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(0 * 4 + s) * 64], xf[X3_PB[t]][s], q, 0, 0, 0);
+                    k = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(1 * 4 + s) * 64], xf[X3_PB[t]][s], k, 0, 0, 0);
+                    vt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[X3_PB[t]][s], wp[(2 * 4 + s) * 64], vt, 0, 0, 0);
                     if (s == 3) __builtin_amdgcn_sched_barrier(0);      // (a term's fragment reads stay with the term: no spills)
                 }
             if (next) park_head(wn);
@@ -257,27 +214,26 @@ __global__ __launch_bounds__(NT) void ta_block_x3_kernel(const TaArgs a) {
             // registers 8 s .. 8 s + 7 are one K fragment
             bf16x8 of[3][2];
 #pragma unroll
-            for (int s = 0; s < 2; ++s)
+            for (int s = 0; s < 2; ++s) {
+                float ov[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    __bf16 ph, pm, pl;
-                    split3(oacc[8 * s + j], ph, pm, pl);
-                    of[0][s][j] = ph; of[1][s][j] = pm; of[2][s][j] = pl;
-                }
+                for (int j = 0; j < 8; ++j) ov[j] = oacc[8 * s + j];
+                split3x8(ov, of[0][s], of[1][s], of[2][s]);
+            }
             const bf16x8* wof = wf + WQKV_E / 8;
 #pragma unroll
             for (int t = 0; t < 6; ++t)
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    const bf16x8* wp = wof + PA[t] * (HEAD_E / 8);
-                    yacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(0 * 2 + s) * 64], of[PB[t]][s], yacc[0], 0, 0, 0);
-                    yacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(1 * 2 + s) * 64], of[PB[t]][s], yacc[1], 0, 0, 0);
+                    const bf16x8* wp = wof + X3_PA[t] * (HEAD_E / 8);
+                    yacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(0 * 2 + s) * 64], of[X3_PB[t]][s], yacc[0], 0, 0, 0);
+                    yacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp[(1 * 2 + s) * 64], of[X3_PB[t]][s], yacc[1], 0, 0, 0);
                 }
         }
         // ---- 3. the next tile's x is requested, then y leaves in two halves of 32 channels through region B: thread (token, half)
         //         adds the residual (L2-warm second read of x) to channels i*32 + half*16 .. + 16 and stores them
         {   // (unconditional: the last tile re-reads itself)
-            const float* xt = a.x + tile_ptr(more ? li + stride : li) + (int64_t)(half * 32) * a.sc;
+            const float* xt = a.x + ta_tile_ptr(a, wk, more ? li + stride : li) + (int64_t)(half * 32) * a.sc;
 #pragma unroll
             for (int c = 0; c < 32; ++c) v[c] = ldu(uni(xt + (int64_t)c * a.sc), toff);
         }
@@ -344,35 +300,18 @@ extern "C" int sdc_pack_tattn_x3(const float* wqkv, const float* wo, void* dst, 
 
 extern "C" int sdc_tattn_block_x3(const float* x, const float* g_pre, const void* wpk, const float* rot, const float* bias, float* y,
                                   int outer, int inner, int Cc, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream) {
-    SDC_REQUIRE(x && g_pre && wpk && y, SDC_ENULL, "sdc_tattn_block_x3: null pointer");
-    SDC_REQUIRE(Cc == 64 && ntok == 32, SDC_EINVAL, "sdc_tattn_block_x3: dim 64 and 32 frames only (got %d, %d)", Cc, ntok);
-    SDC_REQUIRE(outer > 0 && inner > 0 && inner % NS == 0, SDC_EINVAL, "sdc_tattn_block_x3: pixels per image must be a multiple of 8");
-    const int64_t nblk = (int64_t)outer * inner / NS;
-    SDC_REQUIRE(nblk < (1ll << 31), SDC_EINVAL, "sdc_tattn_block_x3: too many sequences");
-    SDC_REQUIRE(((int64_t)31 * st + inner + (int64_t)63 * sc) * 4 < (1ll << 32) && so >= 0 && sc >= 0 && st >= 0, SDC_EINVAL,
-                "sdc_tattn_block_x3: one outer index must span less than 4 GB (32-bit lane offsets)");
+    SDC_REQUIRE(wpk, SDC_ENULL, "sdc_tattn_block_x3: null pointer");
+    TaArgs a;
+    if (const int rc = ta_check_args("sdc_tattn_block_x3", x, g_pre, rot, bias, y, outer, inner, Cc, ntok, so, sc, st, eps, a)) return rc;
+    a.wpk = reinterpret_cast<const __bf16*>(wpk);
     // the weight buffer is fetched with 16-byte and the rotary table with 8-byte vector loads
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wpk) % 16 == 0, SDC_EALIGN, "sdc_tattn_block_x3: the weight buffer must be 16-byte aligned");
     SDC_REQUIRE(!rot || reinterpret_cast<uintptr_t>(rot) % 8 == 0, SDC_EINVAL, "sdc_tattn_block_x3: rot must be 8-byte aligned");
-    TaArgs a;
-    a.x = x; a.g = g_pre; a.wpk = reinterpret_cast<const __bf16*>(wpk); a.rot = rot; a.bias = bias; a.y = y;
-    a.inner = inner; a.nblk = (int)nblk; a.eps = eps; a.so = so; a.sc = sc; a.st = st;
     const size_t ldsb = (size_t)WBUF_B + REGB_B + sizeof(float) * (size_t)(4 * 32 * 33 + 2 * 32 * 16 + 1024);
     static std::atomic<uint64_t> attr{0};
     SDC_LDS_OPTIN(attr, ta_block_x3_kernel, 160 * 1024, "sdc_tattn_block_x3");
-    // one persistent workgroup per CU (141 KB of LDS: one fits), at most one per pixel group; the CU count is queried once per device
-    static std::atomic<int> ncu_of[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { sdc::set_error("sdc_tattn_block_x3: hipGetDevice failed"); return SDC_EHIP; }
-    int ncu = ncu_of[dev].load(std::memory_order_acquire);
-    if (ncu <= 0) {
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
-            sdc::set_error("sdc_tattn_block_x3: cannot read the CU count of device %d", dev);
-            return SDC_EHIP;
-        }
-        ncu_of[dev].store(ncu, std::memory_order_release);
-    }
-    const unsigned grid = (unsigned)(nblk < ncu ? nblk : ncu);
+    unsigned grid = 0;
+    if (const int rc = sdc::ta_grid("sdc_tattn_block_x3", a.nblk, &grid)) return rc;
     hipLaunchKernelGGL(ta_block_x3_kernel, dim3(grid), dim3(NT), ldsb, sdc::as_stream(stream), a);
     return sdc::check_launch("sdc_tattn_block_x3");
 }

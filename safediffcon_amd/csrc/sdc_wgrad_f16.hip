@@ -18,14 +18,13 @@
 // order: deterministic, no atomics.  Every fp16 x fp16 product is exact in fp32, so dW differs from an fp64 weight gradient of the
 // ROUNDED operands by fp32 summation order only.  The bias gradient is an fp32 sum of the unscaled G (fixed order).
 #include "sdc_common.h"
+#include "sdc_f16frag.h"
 #include <cmath>
 #include <cstring>
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WF_NT = 256;
 constexpr int WF_P = 128;                  // output positions per stage

@@ -109,6 +109,27 @@ def test_attn_x3_entries_reject_before_any_launch():
     assert lib.sdc_pack_tattn_x3(P, P, P + 8, None) == SDC_EALIGN
 
 
+def test_the_three_block_entries_report_shared_checks_under_their_own_name():
+    """the argument checks the three entries share (sdc_tablock_tile.h) name the entry that was called"""
+    lib = _lib.get_lib()
+    P = 256
+    ok = dict(outer=2, inner=16, C=64, so=64 * 32 * 16, sc=32 * 16, st=16)
+    entries = {
+        "sdc_tattn_block": lambda a: lib.sdc_tattn_block(P, P, P, P, P, P, P, a["outer"], a["inner"], a["C"], 32, a["so"], a["sc"], a["st"],
+                                                         1e-5, None),
+        "sdc_tattn_block_f16": lambda a: lib.sdc_tattn_block_f16(P, P, P, P, P, P, a["outer"], a["inner"], a["C"], 32, a["so"], a["sc"],
+                                                                 a["st"], 1e-5, None),
+        "sdc_tattn_block_x3": lambda a: lib.sdc_tattn_block_x3(P, P, P, P, P, P, a["outer"], a["inner"], a["C"], 32, a["so"], a["sc"],
+                                                               a["st"], 1e-5, None),
+    }
+    # Cc = 32; an inner that is no multiple of 8; one outer index spanning 4 GB (31 st + inner + 63 sc = 2^30 elements) and more
+    rejected = (dict(C=32), dict(inner=12), dict(st=(2 ** 30 - 16 - 63 * 512) // 31 + 1), dict(sc=1 << 26))
+    for name, call in entries.items():
+        for kw in rejected:
+            assert call(dict(ok, **kw)) == SDC_EINVAL, (name, kw)
+            assert _lib.last_error().startswith(name + ": "), (name, kw, _lib.last_error())
+
+
 def test_routing_table_lists_per_sample_sizes_only():
     lib = _lib.get_lib()
     assert lib.sdc_tattn_block_x3_ok(64, 32, 64 * 64) == 1                # the measured site

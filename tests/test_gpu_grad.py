@@ -1,7 +1,10 @@
 """-m gpu: the backward (VJP) kernels of the fine-tuning path against torch autograd in fp64 (include/sdc.h "backward"):
 weight / bias gradient of every conv form the three U-Nets hold, GroupNorm + scale/shift + SiLU backward, channel
 LayerNorm / RMSNorm backward, SiLU / GELU backward, the nearest-upsample VJP.  Tolerances are relative to the gradient's
-scale (fp32 kernels, fp64 reference: summation order only)."""
+scale (fp32 kernels, fp64 reference: summation order only).  The shapes here are small: the launch branches that only
+production sizes take (sdc_attn_bwd's 1024-slot cap, the 64-piece / 8192-block grids of sdc_gn_silu_bwd, sdc_act_bwd and
+sdc_sumpool2, sdc_chan_norm_bwd with fewer batch slabs than samples) and peaked attention are in tests/test_gpu_grad_paths.py,
+which borrows this file's helpers."""
 import pytest
 import torch
 import torch.nn.functional as F

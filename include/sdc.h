@@ -583,6 +583,33 @@ size_t sdc_pack_gemm_x3_bytes(int Cout, int Cin, int kH, int kW);
 int sdc_pack_gemm_x3(const float* wp, void* out, int Cout, int Cin, int kH, int kW, void* stream);
 int sdc_conv_gemm_x3(const SdcConvDesc* d, const float* x, const void* wb, const float* bias, float* y, void* stream);
 
+/* The 1x1x1 stride-1 convs over a dense layout as exact three-way bf16 operand splits with the weights resident in LDS (DESIGN.md
+ * section 23; csrc/sdc_conv_pw_x3.hip): the arithmetic of sdc_conv_stem_x3 and sdc_conv_gemm_x3 -- fp32 inputs, fp32 accumulation, fp32
+ * outputs, six v_mfma_f32_32x32x16_bf16 per product, the five small terms in accumulators of their own, fixed k order, no K split, no
+ * atomics.  NOT a switch and no buffer of its own: wp is the conv's ordinary packed Wp[ci][co] (any precision's buffer starts with it),
+ * split by every workgroup as it starts.  sdc_conv itself takes this kernel for the shapes sdc_conv_pw_x3_ok lists (route(), after the
+ * split-K decision) at precision 0 and >= 4; at precision 2 and 3 it keeps the literal fp32 kernels.  A 1x1x1 conv has one weight
+ * layout, and every plan records it with the lowest layout code, precision 0, whatever the plan's own precision: 0 cannot be told from
+ * 4 in such a descriptor, so the listed per-sample shapes run here wherever sdc_conv is called on them -- sampler plans of every
+ * precision, forward_train's forward --: fp32-grade arithmetic in another rounding order, like the Winograd modes.
+ *
+ * Covered: 1x1x1 taps, stride 1, no padding or upsampling, output size = input size; positions of a sample contiguous in x0, x1, y and
+ * the residual (strides (., ., H W, W, 1)), D H W a multiple of 4 and at least 128; sample and channel strides multiples of 4, every
+ * pointer 16-byte aligned; Cin0 and Cin1 multiples of 16 with Cin0 + Cin1 a multiple of 32 from 64 on; Cout a multiple of 64 or 96; and
+ * the three bf16 images of a block of output channels -- the widest of 128, 96 and 64 that divides Cout -- within 160 KB of LDS:
+ * Cin0 + Cin1 <= 256 (128 for the 128-wide block).  Optional second
+ * channel-concatenated input, bias and residual: y = (conv(x0 | x1, w) + bias) + residual.
+ *
+ * sdc_conv_pw_x3_ok: 1 where sdc_conv routes the conv here: covered AND measured faster than the fp32 kernel on the same buffers (the
+ * table in csrc/sdc_conv.hip).  Host only, launches nothing, reads the descriptor only (16-byte aligned operands assumed, a residual
+ * where rs[1] != 0), keyed on Cin0, Cin1, Cout and the per-sample volume and never on B: a sample's bits do not depend on its batch.
+ * sdc_conv_pw_x3: the direct launch for every covered descriptor, listed or not (tests, measurement), asynchronous on `stream`, nothing
+ * allocated.  SDC_ENULL for a null d, x0, wp or y, SDC_EINVAL for a descriptor or operands outside the coverage, both before any
+ * launch. */
+int sdc_conv_pw_x3_ok(const SdcConvDesc* d);
+int sdc_conv_pw_x3(const SdcConvDesc* d, const float* x0, const float* x1, const float* wp, const float* bias, const float* residual,
+                   float* y, void* stream);
+
 /* The 3x3x3 stride-1 convs over rows of 16 as Winograd F(2x2x2,3x3x3) with the Cin products formed from exact three-way bf16 operand
  * splits on the bf16 matrix pipe (net.wino_split, samplers only; csrc/sdc_conv_wino_x3.hip): precision 4's
  * algorithm -- the same transforms, passes, folds into the plane pair, bias and GroupNorm epilogue -- with the arithmetic of

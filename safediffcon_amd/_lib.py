@@ -147,6 +147,8 @@ SIGNATURES = {
     "sdc_pack_gemm_x3_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdc_pack_gemm_x3": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _stream]),
     "sdc_conv_gemm_x3": (C.c_int, [C.POINTER(SdcConvDesc), _f32p, C.c_void_p, _f32p, _f32p, _stream]),
+    "sdc_conv_pw_x3_ok": (C.c_int, [C.POINTER(SdcConvDesc)]),
+    "sdc_conv_pw_x3": (C.c_int, [C.POINTER(SdcConvDesc), _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _stream]),
     "sdc_conv_wino3_x3_ok": (C.c_int, [C.POINTER(SdcConvDesc)]),
     "sdc_pack_wino3_x3_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sdc_pack_wino3_x3": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_int, _stream]),

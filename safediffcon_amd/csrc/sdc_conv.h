@@ -116,4 +116,8 @@ int launch_stem_x3(const SdcConvDesc& d, const float* x, const __bf16* wb, const
 bool gemm_x3_covers(const SdcConvDesc& d);     // conv_gemm_x3_kernel runs this descriptor (sdc_conv_gemm_x3_ok: and measured faster)
 int launch_gemm_x3(const SdcConvDesc& d, const float* x, const __bf16* wb, const float* bias, float* y, hipStream_t s);
 
+// defined in sdc_conv_pw_x3.hip (the 1x1x1 convs at precision >= 4)
+int pw_x3_block(int K, int Cout);              // output channels per workgroup of conv_pw_x3_kernel: 128, 64, or 0 where no weight block fits the LDS
+int launch_pw_x3(const ConvArgs& a, hipStream_t s);
+
 }  // namespace sdcconv

@@ -1717,7 +1717,7 @@ std::string wino_misfit(const SdcConvDesc& d, const Operands& op) {
 }
 
 // The kernel a conv runs, as route() picks it
-enum class Kern { F16, WG3S, WG3, WG2S, WG2, WG1, PW2, PW, STEM, DIRECT };
+enum class Kern { F16, WG3S, WG3, WG2S, WG2, WG1, PWX3, PW2, PW, STEM, DIRECT };
 struct Route {
     Kern kern;
     const char* name;     // kernel template instance (sdc_conv_describe)
@@ -1732,6 +1732,53 @@ struct Route {
 
 Route make_route(Kern k, const char* name, double share, int gn_parts = 0, int tile = 0) {
     return Route{k, name, share, gn_parts, 1, false, tile, false, Direct::GEN};
+}
+
+// Pointwise convs over a dense layout, the shape of conv_pw_kernel, conv_pw2_kernel and conv_pw_x3_kernel: 1x1x1 taps, stride 1, no
+// padding or upsampling, whole 16-channel chunks, positions of a sample contiguous in every input (S % 4 == 0), 16-byte aligned operands
+bool pw_dense(const SdcConvDesc& d, const Operands& op) {
+    const bool fast = (d.Cin0 % BK == 0) && (d.Cin1 % BK == 0) && conv_small(d) && d.Cout < (1 << 30);
+    auto dense_in = [&](const int64_t* st) { return st[4] == 1 && st[3] == d.iW && st[2] == (int64_t)d.iH * d.iW && st[0] % 4 == 0 && st[1] % 4 == 0; };
+    return fast && d.kD * d.kH * d.kW == 1 && d.sD == 1 && d.sH == 1 && d.sW == 1 && d.uD == 1 && d.uH == 1 &&
+        d.uW == 1 && d.up_mode == 0 && d.pD == 0 && d.pH == 0 && d.pW == 0 && d.oD == d.iD && d.oH == d.iH && d.oW == d.iW &&
+        (int64_t)d.oD * d.oH * d.oW % 4 == 0 && d.Cout % 4 == 0 && d.Cout > 32 && dense_in(d.x0s) && (d.Cin1 == 0 || dense_in(d.x1s)) &&
+        aligned(op.x0, 16) && (d.Cin1 == 0 || aligned(op.x1, 16)) && aligned(op.wp, 16);
+}
+
+// ... with whole 16-byte aligned dense rows of y (and of the residual): conv_pw2_kernel's and conv_pw_x3_kernel's epilogues
+bool pw_dense_out(const SdcConvDesc& d, const Operands& op) {
+    const bool al16 = aligned(op.y, 16) && d.ys[0] % 4 == 0 && d.ys[1] % 4 == 0 &&
+                      (!op.res || (aligned(op.res, 16) && d.rs[0] % 4 == 0 && d.rs[1] % 4 == 0));
+    return al16 && y_dense(d, op.res != nullptr);
+}
+
+// Coverage of conv_pw_x3_kernel (sdc_conv_pw_x3.hip): the two predicates above, K = Cin0 + Cin1 a whole number of 32-channel step pairs
+// (at least two), and a block of 128, 96 or 64 output channels that divides Cout and whose three bf16 images fit the LDS (K <= 128, 256
+// and 256).  Per-sample sizes, strides and alignment only, never B.
+bool pw_x3_covers(const SdcConvDesc& d, const Operands& op) {
+    const int K = d.Cin0 + d.Cin1;
+    // (a lane's offset walks the 16 channels of a k chunk besides the sample and the position)
+    auto lane_span = [&](const int64_t* st) { return (int64_t)(d.B - 1) * st[0] + (int64_t)d.oD * d.oH * d.oW + 16 * st[1] < (1ll << 30); };
+    return pw_dense(d, op) && pw_dense_out(d, op) && K >= 64 && K % 32 == 0 && pw_x3_block(K, d.Cout) > 0 &&
+           lane_span(d.x0s) && (d.Cin1 == 0 || lane_span(d.x1s));
+}
+
+const char* pw_x3_name(int mb) { return mb == 128 ? "conv_pw_x3_kernel<4,2>" : mb == 96 ? "conv_pw_x3_kernel<3,2>" : "conv_pw_x3_kernel<2,2>"; }
+
+// The routing table of conv_pw_x3_kernel: the shapes where every repeat of sdc_conv_pw_x3 measured faster than
+// every repeat of the fp32 kernel (sdc_conv at precision 3: conv_pw2_kernel) on the same buffers at the bench batch
+// (profiles/pw_x3_shapes.log, row for row).  Keyed on Cin0, Cin1, Cout and the per-sample volume, never on B.
+bool pw_x3_faster(const SdcConvDesc& d) {
+    struct Row { int cin0, cin1, cout, S; };
+    static const Row rows[] = {
+        {128, 0, 384, 32 * 32 * 32}, {256, 0, 384, 32 * 16 * 16}, {128, 0, 256, 32 * 16 * 16}, {64, 64, 64, 32 * 64 * 64},
+        {128, 0, 128, 32 * 32 * 32}, {128, 128, 64, 32 * 32 * 32}, {128, 0, 384, 32 * 16 * 16}, {64, 0, 128, 32 * 32 * 32},
+        {128, 0, 128, 32 * 16 * 16},
+    };
+    const int64_t S = (int64_t)d.oD * d.oH * d.oW;
+    for (const Row& r : rows)
+        if (d.Cin0 == r.cin0 && d.Cin1 == r.cin1 && d.Cout == r.cout && S == r.S) return true;
+    return false;
 }
 
 // The one place that decides which kernel a conv runs: sdc_conv, sdc_conv_gn, sdc_conv_splitk and sdc_conv_dgrad_f16 (conv_impl,
@@ -1803,11 +1850,7 @@ Route route(const SdcConvDesc& d, const Operands& op, int G, bool split) {
         return r;
     };
     // pointwise convs over a dense layout: 16-byte loads of weights and activations
-    auto dense_in = [&](const int64_t* st) { return st[4] == 1 && st[3] == d.iW && st[2] == (int64_t)d.iH * d.iW && st[0] % 4 == 0 && st[1] % 4 == 0; };
-    const bool pw = fast && d.kD * d.kH * d.kW == 1 && d.sD == 1 && d.sH == 1 && d.sW == 1 && d.uD == 1 && d.uH == 1 &&
-        d.uW == 1 && d.up_mode == 0 && d.pD == 0 && d.pH == 0 && d.pW == 0 && d.oD == d.iD && d.oH == d.iH && d.oW == d.iW &&
-        (int64_t)d.oD * d.oH * d.oW % 4 == 0 && d.Cout % 4 == 0 && d.Cout > 32 && dense_in(d.x0s) && (d.Cin1 == 0 || dense_in(d.x1s)) &&
-        aligned(op.x0, 16) && (d.Cin1 == 0 || aligned(op.x1, 16)) && aligned(op.wp, 16);
+    const bool pw = pw_dense(d, op);
     // sdc_conv_splitk on the direct-form kernels' smallest tile: K split, the bias added by splitk_sum_kernel
     const int sd = (splits && d.oW % 4 == 0 && d.precision != 5) ? direct_ksplit(d, ntot, fast) : 1;
     if (sd > 1) {
@@ -1817,11 +1860,16 @@ Route route(const SdcConvDesc& d, const Operands& op, int G, bool split) {
         return r;
     }
     if (pw) {
+        // exact bf16 splits with LDS-resident weights (sdc_conv_pw_x3.hip) for the per-sample shapes of the measured table -- fp32-grade
+        // arithmetic in another rounding order, like the Winograd modes.  The precision field cannot gate it at 4: a 1x1x1 conv has one
+        // weight layout, so every plan, whatever its precision, records these convs with the lowest layout code, 0 (engine.py
+        // conv_precision; the recorded descriptors are pinned).  0 therefore routes like >= 4; 2 and 3, which only a direct caller
+        // writes into a 1x1x1 descriptor, keep the literal fp32 kernels (the baseline of tools/f16_step.py --pw-split)
+        if (d.precision != 2 && d.precision != 3 && pw_x3_faster(d) && pw_x3_covers(d, op))
+            return make_route(Kern::PWX3, pw_x3_name(pw_x3_block(d.Cin0 + d.Cin1, d.Cout)), 0.0);
         // two-workgroups-per-CU form with interleaved tiles (round 5): whole 128-channel blocks, 16-byte aligned dense rows of y
         // (and of the residual), enough 128 x 256 tiles for two rounds of the chip
-        const bool al16 = aligned(op.y, 16) && d.ys[0] % 4 == 0 && d.ys[1] % 4 == 0 &&
-                          (!op.res || (aligned(op.res, 16) && d.rs[0] % 4 == 0 && d.rs[1] % 4 == 0));
-        const bool pw2 = al16 && y_dense(d, op.res != nullptr);
+        const bool pw2 = pw_dense_out(d, op);
         if (pw2 && d.Cout % 128 == 0 && ((ntot + 255) / 256) * (d.Cout / 128) >= 1024) return make_route(Kern::PW2, "conv_pw2_kernel<2,2>", 1.0, 0, 0);
         if (pw2 && d.Cout == 64 && (ntot + 511) / 512 >= 1024) return make_route(Kern::PW2, "conv_pw2_kernel<1,4>", 1.0, 0, 1);
         if (d.Cout > 64 && ntot >= 128 * 256) return make_route(Kern::PW, "conv_pw_kernel<128,128,2,2>", 1.0, 0, 0);
@@ -1952,6 +2000,35 @@ extern "C" int sdc_conv_describe(const SdcConvDesc* dp, char* name, size_t cap, 
     return SDC_OK;
 }
 
+// conv_pw_x3_kernel (include/sdc.h): the routing table route() consults (at every precision but 2 and 3), and the direct launch for every
+// covered descriptor.  The descriptor-only query assumes 16-byte aligned operands and takes the residual from the descriptor's strides.
+extern "C" int sdc_conv_pw_x3_ok(const SdcConvDesc* dp) {
+    if (!dp || check_conv(*dp, CANONICAL, false) != SDC_OK) return 0;
+    Operands op = CANONICAL;
+    if (dp->rs[1] != 0) op.res = ALIGNED;
+    return pw_x3_faster(*dp) && pw_x3_covers(*dp, op) ? 1 : 0;
+}
+
+extern "C" int sdc_conv_pw_x3(const SdcConvDesc* dp, const float* x0, const float* x1, const float* wp, const float* bias,
+                              const float* residual, float* y, void* stream) {
+    SDC_REQUIRE(dp && x0 && wp && y, SDC_ENULL, "sdc_conv_pw_x3: null pointer");
+    const SdcConvDesc& d = *dp;
+    const Operands op{x0, x1, wp, y, residual};
+    { const int rc = check_conv(d, op, false); if (rc != SDC_OK) return rc; }
+    SDC_REQUIRE(pw_x3_covers(d, op), SDC_EINVAL, "sdc_conv_pw_x3: descriptor not covered: %dx%dx%d taps, stride %dx%dx%d, Cin %d+%d, Cout %d, "
+                "output %dx%dx%d (1x1x1 stride-1 convs over dense 16-byte aligned operands, Cin a multiple of 32 from 64 to 256, Cout a "
+                "multiple of 64 or 96, the weight block within the LDS: include/sdc.h)", d.kD, d.kH, d.kW, d.sD, d.sH, d.sW, d.Cin0, d.Cin1, d.Cout,
+                d.oD, d.oH, d.oW);
+    ConvArgs a{};
+    a.d = d;
+    a.x0 = x0; a.x1 = x1; a.wp = wp; a.bias = bias; a.res = residual; a.y = y;
+    a.Ntot = d.B * d.oD * d.oH * d.oW;
+    a.Cin = d.Cin0 + d.Cin1;
+    a.Ktot = a.Cin;
+    a.ksplit = 1;
+    return launch_pw_x3(a, sdc::as_stream(stream));
+}
+
 // net.stem_f16 (include/sdc.h): the covered 7-tap stem convs with fp16 operands and fp32 accumulation, on their own fp16 buffer
 extern "C" int sdc_conv_stem_f16_ok(const SdcConvDesc* dp) {
     return dp && stem_f16_ok(*dp) ? 1 : 0;
@@ -2051,6 +2128,7 @@ int conv_impl(const SdcConvDesc* dp, const float* x0, const float* x1, const flo
                     rc = r.ups ? launch_wg<64, 128, 2, 2, 16, 256, true>(a, s) : launch_wg<64, 128, 2, 2, 16, 512, false, 4, 2>(a, s);
             }
             break;
+        case Kern::PWX3: rc = launch_pw_x3(a, s); break;
         case Kern::PW2: rc = r.tile == 0 ? launch_pw2<2, 2>(a, s) : launch_pw2<1, 4>(a, s); break;
         case Kern::PW:
             switch (r.tile) {

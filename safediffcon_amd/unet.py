@@ -339,6 +339,10 @@ class _HipUNet(nn.Module):
         # measured routing table lists (sdc_conv_gemm_x3_ok; per-sample sizes only, so a sample's bits do not depend on its batch).
         # fp32-grade like stem_split; precision 0, 2 and 3, forward_train, GraphedLossStep, the differentiable DDIM step, split-K convs
         # and the conditioning MLP never see it.  False = the fp32 kernels (A/B checks).  Read when a plan is built.
+        # (The table lists no 1x1x1 conv.  Those run as exact bf16 splits behind sdc_conv itself, whatever this switch and net.precision
+        # say: sdc_conv takes conv_pw_x3_kernel for the per-sample shapes of sdc_conv_pw_x3_ok wherever it is called -- sampler plans of
+        # every precision (they record a 1x1x1 conv with the layout code 0), forward_train's forward -- fp32-grade in another rounding
+        # order like the Winograd modes)
         self.gemm_split = True
         # the 3x3x3 convs of the sampler plans at precision 4 and 5 as Winograd F(2x2x2,3x3x3) with the same exact three-way bf16 splits of
         # the transformed operands (conv_wg3_x3_kernel), GroupNorm sums in the epilogue included, for the shapes that the library's

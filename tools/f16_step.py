@@ -23,6 +23,12 @@
       (strided (1,4,4), sub-pixel (1,2,2), 1x1x1; routed or not), sdc_conv at precision 4 against sdc_conv_gemm_x3 on the same buffers, the
       medians of 20 launches in three interleaved repeats -- the data of the routing table (sdc_conv_gemm_x3_ok, DESIGN section 15: a
       shape qualifies when every repeat beats every repeat of the fp32 kernel); then the C4 sampler step with the switch off against on
+  python tools/f16_step.py --pw-split [--workloads c4,c2,c3] [--no-step]
+      conv_pw_x3_kernel (csrc/sdc_conv_pw_x3.hip): every 1x1 conv of the nets' forward plans that sdc_conv_pw_x3 accepts
+      (listed or not), sdc_conv at precision 3 (a 1x1 descriptor at 2 or 3 keeps the fp32 kernel the parent runs) against sdc_conv_pw_x3 on the same buffers,
+      the medians of 20 launches in three interleaved repeats at the bench batch and at B = 2 -- the data of the routing table
+      (sdc_conv_pw_x3_ok: a shape qualifies when every repeat beats every repeat of the fp32 kernel at the bench batch); then the C4 and
+      C2 steps of this build (sdc_conv carries no switch: the step's A/B is by commit, SDC_LIB_PATH naming the parent's library)
   python tools/f16_step.py --wino [--steps 20] [--warmup 5] [--rounds 3] [--no-step]
       net.wino_split (csrc/sdc_conv_wino_x3.hip): every 3x3x3 conv of the C4 switch-off plan that conv_wg3_x3_kernel covers (routed or
       not), sdc_conv / sdc_conv_gn at precision 4 against sdc_conv_wino3_x3 on the same buffers (GroupNorm sums in both where the plan
@@ -329,6 +335,73 @@ def gemm_shapes(names):
         torch.cuda.empty_cache()
 
 
+def pw_shapes(names):
+    """every 1x1 conv of the forward plans that sdc_conv_pw_x3 accepts: the fp32 kernel (sdc_conv at precision 3) against it, same buffers"""
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    nets = {
+        "c4": (lambda: sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7), (64, 32, 7, 64, 64)),
+        "c2": (lambda: sdc.Unet2D(dim=64, dim_mults=(1, 2, 4, 8), channels=3, resnet_block_groups=1), (256, 3, 16, 128)),
+        "c3": (lambda: sdc.Unet1D(dim=256, dim_mults=(1, 2, 4, 8), channels=12, resnet_block_groups=1), (128, 12, 128)),
+    }
+    name_buf = C.create_string_buffer(96)
+    share = C.c_double(0.0)
+    for wl in names:
+        make, shape = nets[wl]
+        torch.manual_seed(0)
+        net = make().to(DEV)
+        x = torch.randn(shape, device=DEV) * 0.5
+        t = torch.full((shape[0],), 500, device=DEV, dtype=torch.long)
+        with torch.no_grad():
+            net(x, t)
+            plan = net.entry(tuple(shape), shape[0])["plan"]
+        seen, tot0, totx, totq = {}, 0.0, 0.0, 0.0
+        for fn, args in plan.calls:
+            if fn.__name__ != "sdc_conv":
+                continue
+            d = args[0]._obj
+            if d.kD * d.kH * d.kW != 1:
+                continue
+            key = (d.Cin0, d.Cin1, d.Cout, d.oD, d.oH, d.oW, int(bool(args[5])))
+            desc = f"{wl} 1x1x1 Cin {d.Cin0}+{d.Cin1} Cout {d.Cout} {d.oD}x{d.oH}x{d.oW} res {key[-1]}"
+            rows = []
+            for B in (d.B, 2):
+                d0, dx = type(d).from_buffer_copy(d), type(d).from_buffer_copy(d)          # (the first B samples of the same buffers)
+                d0.B = dx.B = B
+                d0.precision = 3                                # (never routed to the split kernel: the name is printed)
+                rest = tuple(args[1:7])
+                rc = lib.sdc_conv_pw_x3(C.byref(dx), *rest, stream)
+                if rc != 0:
+                    print(f"{desc}: not covered ({_lib.last_error()})", flush=True)
+                    rows = None
+                    break
+                lib.sdc_conv_describe(C.byref(d0), name_buf, 96, C.byref(share))
+                m0, mx = [], []
+                for _ in range(3):      # interleaved repeats of the median of 20: their spread is what a gain has to beat
+                    m0.append(_time_call(lib.sdc_conv, (C.byref(d0), *rest), stream))
+                    mx.append(_time_call(lib.sdc_conv_pw_x3, (C.byref(dx), *rest), stream))
+                rows.append((B, name_buf.value.decode(), m0, mx))
+            if rows is None:
+                continue
+            (B, kname, m0, mx), (_, kname2, n0, nx) = rows
+            flop = 2.0 * B * d.oD * d.oH * d.oW * d.Cout * (d.Cin0 + d.Cin1)
+            a0, ax = statistics.median(m0), statistics.median(mx)
+            q = max(mx) < min(m0)
+            tot0 += a0
+            totx += ax
+            totq += ax if q else a0
+            seen[key] = seen.get(key, 0) + 1
+            print(f"[measured] {desc} B {B}: fp32 {kname} {' / '.join(f'{v * 1e3:.1f}' for v in m0)} us ({flop / a0 / 1e9:.0f} TFLOP/s) | "
+                  f"conv_pw_x3_kernel {' / '.join(f'{v * 1e3:.1f}' for v in mx)} us ({flop / ax / 1e9:.0f} TFLOP/s direct-form) -> x{a0 / ax:.2f} "
+                  f"{'QUALIFIES' if q else 'stays'}; B 2: {kname2} {' / '.join(f'{v * 1e3:.1f}' for v in n0)} | "
+                  f"{' / '.join(f'{v * 1e3:.1f}' for v in nx)} us -> x{statistics.median(n0) / statistics.median(nx):.2f}; "
+                  f"table says {int(lib.sdc_conv_pw_x3_ok(C.byref(d)))}{' (repeat)' if seen[key] > 1 else ''}", flush=True)
+        print(f"[measured] {wl}: the covered 1x1 convs of one forward: fp32 kernels {tot0:.2f} ms, split {totx:.2f} ms, "
+              f"qualifying ones routed {totq:.2f} ms", flush=True)
+        del net, plan
+        torch.cuda.empty_cache()
+
+
 def wino_shapes():
     """every 3x3x3 conv of the C4 switch-off forward plan that sdc_conv_wino3_x3 accepts: today's kernel against it, same buffers"""
     from safediffcon_amd.engine import pack_wino3_x3
@@ -596,12 +669,13 @@ if __name__ == "__main__":
     ap.add_argument("--stem", action="store_true", help="net.stem_f16: the stem launch and the C4 step (with --drift: the stem arms)")
     ap.add_argument("--split", action="store_true", help="net.stem_split: the stem launch and the C4 step with the switch off / on")
     ap.add_argument("--gemm", action="store_true", help="net.gemm_split: the covered convs, launch by launch, and the C4 step with the switch off / on")
+    ap.add_argument("--pw-split", action="store_true", help="conv_pw_x3_kernel: the covered 1x1 convs, launch by launch, against the fp32 kernel; then the C4 and C2 steps of this build (the A/B is by commit: SDC_LIB_PATH)")
     ap.add_argument("--wino", action="store_true", help="net.wino_split: the covered 3x3x3 convs, launch by launch, and the C4 step with the switch off / on")
     ap.add_argument("--attn", action="store_true", help="net.attn_f16: the block launch and the C4 step (with --drift: 4 + attn_f16 against 4)")
     ap.add_argument("--linattn", action="store_true", help="net.linattn_f16: the block launch at the C4 / C2 sites, the C4 and C2 steps (with --drift: 4 + linattn_f16 against 4)")
     ap.add_argument("--linattn-split", action="store_true", help="the fused LinearAttention block, impl 0 (fp32) against impl 1 (bf16-split q / k projections) launch by launch; then the C4 and C2 steps of this build (the A/B is by commit: SDC_LIB_PATH)")
     ap.add_argument("--attn-split", action="store_true", help="net.attn_split: the block launch at the sites of the dim-64 smoke net and the C4 step with the switch off / on")
-    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --wino / --attn / --attn-split: the per-shape part only")
+    ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --pw-split / --wino / --attn / --attn-split: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
     if a.drift:
@@ -611,6 +685,10 @@ if __name__ == "__main__":
         if not a.no_step:
             # the entry points carry no switch: the step's A/B is by commit (bench.py of the two checkouts, or SDC_LIB_PATH naming the
             # parent's library for a second run of this command)
+            step_ab([w for w in wls if w in ("c4", "c2")], a.steps, a.warmup, a.rounds, arms=[4])
+    elif a.pw_split:
+        pw_shapes(wls)
+        if not a.no_step:
             step_ab([w for w in wls if w in ("c4", "c2")], a.steps, a.warmup, a.rounds, arms=[4])
     elif a.linattn:
         linattn_shapes()

@@ -36,6 +36,8 @@ def classify(lib, fn, a):
             kind += " [Winograd F(4,3) along W]"
         elif "conv_wg" in kern:
             kind += " [Winograd F(2,3) along W]"
+        elif "conv_pw_x3" in kern:
+            kind += " [bf16 split: exact 3-way operand splits on the bf16 matrix pipe, weights resident in LDS]"      # (share 0: no fp32 MFMA)
         if fn is lib.sdc_conv_gn:
             kind += " + GroupNorm statistics in the epilogue"
         if split:

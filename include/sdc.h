@@ -702,6 +702,23 @@ size_t sdc_attn_bwd_bytes(int outer, int inner, int heads, int ntok);
 int sdc_attn_bwd(const float* qkv, const float* dout, const float* rot, const float* bias, float* dqkv, float* dbias, void* work,
                  int outer, int inner, int heads, int ntok, int64_t q_so, int64_t q_sc, int64_t q_si, int64_t q_st,
                  int64_t o_so, int64_t o_sc, int64_t o_si, int64_t o_st, void* stream);
+
+/* Backward of sdc_tattn_block for fine-tuning (net.train_fuse_attn; csrc/sdc_tablock_bwd.hip): from x and dy
+ * alone -- xn, q/k/v, P, O and every gradient of an intermediate are recomputed on chip, nothing full-size is written but dx.
+ * x, g_pre, wqkv (packed [64][384]), wo (packed [128][64]), rot, bias, the strides and the supported domain (C = 64, 32 frames,
+ * inner a multiple of 8, one outer index below 4 GB) are sdc_tattn_block's; dy and dx are addressed as x.
+ *   dx    = dy + J^T dy (the residual branch included)        dg [64]
+ *   dwqkv, dwo: the layouts of wqkv and wo                     dbias [4][32][32]: required exactly when bias is given, ignored otherwise
+ * Outputs are overwritten, not accumulated.  dx must not alias x or dy (x is read again after dx of a neighbouring tile is written).
+ * work = sdc_tattn_block_bwd_bytes(outer, inner) bytes: one table of parameter-gradient partial sums per workgroup, summed in a
+ * fixed order (deterministic, no atomics); its content before the call does not matter.  The size is an upper bound that needs no
+ * device query and stops growing at 256 pixel groups.
+ * Checked before any launch or device query: SDC_ENULL for a null x, g_pre, wqkv, wo, dy, dx, dg, dwqkv, dwo or work, and for bias
+ * without dbias; SDC_EINVAL for an unsupported shape, a wqkv / wo not 16-byte or a rot not 8-byte aligned. */
+size_t sdc_tattn_block_bwd_bytes(int outer, int inner);
+int sdc_tattn_block_bwd(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* rot, const float* bias,
+                        const float* dy, float* dx, float* dg, float* dwqkv, float* dwo, float* dbias, void* work,
+                        int outer, int inner, int C, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream);
 size_t sdc_linattn_bwd_bytes(int outer, int inner, int heads, int64_t n);      /* scratch of sdc_linattn_bwd */
 int sdc_linattn_bwd(const float* qkv, const float* dout, float* dqkv, void* work, int outer, int inner, int heads, int64_t n,
                     int64_t q_so, int64_t q_sc, int64_t q_si, int64_t o_so, int64_t o_sc, int64_t o_si, void* stream);

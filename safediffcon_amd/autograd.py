@@ -108,6 +108,14 @@ def check_train_precision(v):
     return int(v)
 
 
+def check_train_fuse_attn(v):
+    """net.train_fuse_attn: False (the chain of nodes, the default) or True (the fused temporal-attention node where it covers the
+    site); only booleans, anything else raises ValueError"""
+    if not isinstance(v, bool):
+        raise ValueError(f"train_fuse_attn must be True or False (got {v!r})")
+    return v
+
+
 def f16_train_form(k, stride, pad, up):
     """the conv forms train_precision 6 / 7 route to the fp16 kernels: 1x1x3 / 1x3x3 / 3x3x3 taps, stride 1, pad 1 along every
     3-wide axis, no folded upsampling (the kernels' own coverage -- row widths, LDS -- is checked by the library)"""
@@ -430,6 +438,30 @@ class AttnCoreFn(Function):
         return dqkv, dbias, None, None
 
 
+class TemporalBlockFn(Function):
+    """Residual(PreNorm(temporal Attention)) of the smoke net at width 64, 32 frames as ONE node (net.train_fuse_attn): forward
+    sdc_tattn_block, backward sdc_tattn_block_bwd.  Saved for backward: x, the parameters and the two small tables -- no intermediate
+    (the backward recomputes xn, q/k/v and P from x).  wqkv (384, 64) and wo (64, 128) are the nn.Linear weights; the kernels read
+    their transposes (the packed [64][384] / [128][64] tables: 32 K floats, copied per call), and the weight gradients come back in
+    the parameters' own layouts.  rot has no gradient; the bias gradient flows on through the gather it came from."""
+
+    @staticmethod
+    def forward(ctx, x, g, wqkv, wo, rot, bias):
+        gd = g.detach().reshape(-1).contiguous()
+        wqkv_p, wo_p = wqkv.detach().t().contiguous(), wo.detach().t().contiguous()
+        bd = None if bias is None else bias.detach().contiguous()
+        ctx.save_for_backward(x, gd, wqkv, wo, rot, bd)
+        ctx.gshape = g.shape
+        return grad_ops.tattn_block(x, gd, wqkv_p, wo_p, rot, bd)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gd, wqkv, wo, rot, bd = ctx.saved_tensors
+        wqkv_p, wo_p = wqkv.detach().t().contiguous(), wo.detach().t().contiguous()
+        dx, dg, dwqkv_p, dwo_p, dbias = grad_ops.tattn_block_bwd(x, gd, wqkv_p, wo_p, rot, bd, gy.contiguous())
+        return dx, dg.reshape(ctx.gshape), dwqkv_p.t().contiguous(), dwo_p.t().contiguous(), None, dbias
+
+
 class LinAttnCoreFn(Function):
     """linear attention core (sdc_linattn / sdc_linattn_bwd); geom = (heads, outer, inner, n, q strides, out strides, out shape)"""
 
@@ -476,11 +508,13 @@ class Trainer:
         self.prec = 4 if net.precision in (6, 7) else net.precision
         self.arena = grad_ops.PackArena()
         self.tprec = None        # net.train_precision, read at the start of every training forward (step)
+        self.fuse_attn = False   # net.train_fuse_attn, likewise
 
     @contextlib.contextmanager
     def step(self, device):
         """one training forward: every packed conv weight refreshed by one launch, conv nodes bound to this net's arena"""
         self.tprec = check_train_precision(getattr(self.net, "train_precision", None))
+        self.fuse_attn = check_train_fuse_attn(getattr(self.net, "train_fuse_attn", False))
         self.arena.begin(device)
         prev, _ARENA.cur = _ARENA.cur, self.arena
         try:
@@ -577,6 +611,10 @@ class Trainer:
         B, Cc, Fr, H, W = x.shape
         hw = H * W
         rot, bias = tables
+        if self.fuse_attn and self.net.fuse_linattn and Cc == 64 and Fr == 32 and hw % 8 == 0 and x.is_contiguous():
+            # the sites the sampler plans fuse (unet.py, temporal): one node, nothing but x saved
+            return TemporalBlockFn.apply(x, self.P(f"{p}.fn.norm.gamma"), self.P(f"{p}.fn.fn.fn.to_qkv.weight"),
+                                         self.P(f"{p}.fn.fn.fn.to_out.weight"), rot, bias)
         xn = ChanNormFn.apply(x, self.P(f"{p}.fn.norm.gamma"), 0)
         qkv = self._pw(f"{p}.fn.fn.fn.to_qkv.weight", xn)
         o = AttnCoreFn.apply(qkv, bias, rot, (HEADS, B, hw, Fr, (3 * HID * Fr * hw, Fr * hw, 1, hw), (HID * Fr * hw, Fr * hw, 1, hw),

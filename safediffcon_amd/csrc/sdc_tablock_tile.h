@@ -1,8 +1,9 @@
 // Tile helpers shared by the fused temporal-attention block kernels (sdc_tablock.hip: fp32 operands; sdc_tablock_f16.hip: fp16
-// operands; sdc_tablock_x3.hip: bf16-split projections): the kernel arguments, the tile geometry, the wave-uniform-base global
-// accesses, the workgroup walk, and the host entries' common checks and grid choice.
+// operands; sdc_tablock_x3.hip: bf16-split projections; sdc_tablock_bwd.hip: the fp32 block's backward): the kernel arguments,
+// the tile geometry, the wave-uniform-base global accesses, the workgroup walk, and the host entries' common checks and grid choice.
 //
-// The three kernels differ in their weight arguments only.  A translation unit names them before it includes this header,
+// The three forward kernels differ in their weight arguments only (the backward adds dy and its workspace there; its y is dx).
+// A translation unit names them before it includes this header,
 //   #define TA_WEIGHT_ARGS const float* wqkv; const float* wo;
 // and gets its own TaArgs (the kernels' symbol names carry the type's name, the kernel arguments its layout).
 #pragma once

@@ -197,6 +197,40 @@ def attn_core_bwd(qkv, dout, heads, outer, inner, ntok, qs, os_, rot=None, bias=
     return dqkv, dbias
 
 
+def _tattn_geom(x):
+    B, Cc, Fr, H, W = x.shape
+    hw = H * W
+    return B, hw, Cc, Fr, Cc * Fr * hw, Fr * hw, hw
+
+
+def tattn_block(x, g, wqkv_p, wo_p, rot, bias, eps=1e-5):
+    """the fused temporal-attention block in fp32 (sdc_tattn_block): x (B, 64, 32, H, W) contiguous, g (64), wqkv_p packed [64][384],
+    wo_p packed [128][64], rot [32][16][2] or None, bias (4, 32, 32) or None -> y"""
+    _need_cuda(x, g, wqkv_p, wo_p, rot, bias)
+    lib = _lib.get_lib()
+    y = torch.empty_like(x)
+    check(lib.sdc_tattn_block(x.data_ptr(), g.data_ptr(), wqkv_p.data_ptr(), wo_p.data_ptr(), 0 if rot is None else rot.data_ptr(),
+                              0 if bias is None else bias.data_ptr(), y.data_ptr(), *_tattn_geom(x), eps, _stream(x)), "sdc_tattn_block")
+    return y
+
+
+def tattn_block_bwd(x, g, wqkv_p, wo_p, rot, bias, dy, eps=1e-5, work=None):
+    """backward of tattn_block from x and dy alone (sdc_tattn_block_bwd) -> (dx, dg, dwqkv_p, dwo_p, dbias | None); the gradients
+    of the weights come in the packed layouts of wqkv_p and wo_p"""
+    _need_cuda(x, g, wqkv_p, wo_p, rot, bias, dy)
+    lib = _lib.get_lib()
+    geom = _tattn_geom(x)
+    dx, dg, dwqkv, dwo = torch.empty_like(x), torch.empty_like(g), torch.empty_like(wqkv_p), torch.empty_like(wo_p)
+    dbias = None if bias is None else torch.empty_like(bias)
+    if work is None:
+        work = torch.empty(int(lib.sdc_tattn_block_bwd_bytes(geom[0], geom[1])) // 4, dtype=torch.float32, device=x.device)
+    check(lib.sdc_tattn_block_bwd(x.data_ptr(), g.data_ptr(), wqkv_p.data_ptr(), wo_p.data_ptr(), 0 if rot is None else rot.data_ptr(),
+                                  0 if bias is None else bias.data_ptr(), dy.data_ptr(), dx.data_ptr(), dg.data_ptr(), dwqkv.data_ptr(),
+                                  dwo.data_ptr(), 0 if dbias is None else dbias.data_ptr(), work.data_ptr(), *geom, eps, _stream(x)),
+          "sdc_tattn_block_bwd")
+    return dx, dg, dwqkv, dwo, dbias
+
+
 def linattn_core(qkv, out, heads, outer, inner, n, qs, os_):
     """linear attention core (sdc_linattn): strides (so, sc, si) of qkv and out"""
     lib = _lib.get_lib()

@@ -307,6 +307,14 @@ class _HipUNet(nn.Module):
         # strided, upsampling, stem convs, attention, linear layers, norms) stays fp32.  No effect on net(x, t) or the samplers; a
         # live GraphedLossStep keeps the mode it was captured with.  Other values raise ValueError.
         self.train_precision = None
+        # fine-tuning (forward_train: p_losses, GraphedLossStep, the differentiable last DDIM step), read at every forward_train:
+        # False (default) = the temporal-attention blocks as today's chain of nodes (norm -> 1x1 -> core -> 1x1 -> add), bit for bit;
+        # True (opt-in) = the sites the sampler plans fuse (width 64, 32 frames, H W % 8 == 0, contiguous, fuse_linattn on) as ONE node:
+        # forward sdc_tattn_block (literal fp32), backward sdc_tattn_block_bwd, which recomputes everything from x and dy -- only x is
+        # saved instead of x, xn, qkv and the attention output (9x the bytes of x less per site).  fp32 in another summation order;
+        # independent of train_precision.  Wider sites, the 1-D nets, net(x, t) and the samplers never see it; a live GraphedLossStep
+        # keeps the mode it was captured with.  Only booleans are accepted (ValueError otherwise).
+        self.train_fuse_attn = False
         # 7-tap stem conv (init_conv) of the sampler plans -- model(x, t), graph-replayed or eager, and the samplers -- on the fp16
         # matrix pipe (opt-in): fp16 operands rounded to nearest even, fp32 accumulation, where conv_stem_f16_kernel covers it
         # (Cin <= 8, Cout a multiple of 64, rows of 16 / 32 / 64 / 128: the smoke and Burgers stems at production width; the tokamak
@@ -397,6 +405,15 @@ class _HipUNet(nn.Module):
     def train_precision(self, v):
         from .autograd import check_train_precision
         self.__dict__["_train_precision"] = check_train_precision(v)
+
+    @property
+    def train_fuse_attn(self):
+        return self.__dict__.get("_train_fuse_attn", False)
+
+    @train_fuse_attn.setter
+    def train_fuse_attn(self, v):
+        from .autograd import check_train_fuse_attn
+        self.__dict__["_train_fuse_attn"] = check_train_fuse_attn(v)
 
     def P(self, key):
         m = self

@@ -719,6 +719,29 @@ size_t sdc_tattn_block_bwd_bytes(int outer, int inner);
 int sdc_tattn_block_bwd(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* rot, const float* bias,
                         const float* dy, float* dx, float* dg, float* dwqkv, float* dwo, float* dbias, void* work,
                         int outer, int inner, int C, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream);
+
+/* Backward of sdc_linattn_block_sel(..., impl = 0) for fine-tuning (net.train_fuse_linattn; DESIGN.md section 25;
+ * csrc/sdc_lablock_bwd.hip), SpatialLinearAttention form only: pre_mode 0 (channel LayerNorm), post_mode -1 (no post norm).  From x
+ * and dy alone -- xn, Q, K, the two softmaxes, dQ, dK and dxn are recomputed tile by tile on chip (V is never formed per token);
+ * nothing of size C x tokens is written but dx.  x, g_pre, wqkv (packed [C][384]), wo (packed [128][C]), the strides and the domain
+ * (C in {64, 128}, n % 64 == 0, outer * inner < 65536, sc < 2^27) are sdc_linattn_block's; dy and dx are addressed as x.
+ *   dx    = dy + J^T dy (the residual branch included)        dg [C]
+ *   dwqkv, dwo: the layouts of wqkv and wo                     dbo [C]: required exactly when bo is given, not written otherwise
+ *                                                              (bo is only tested for null)
+ * Outputs are overwritten, not accumulated.  dx must not alias x or dy (x and dy are read twice).
+ * work = sdc_linattn_block_bwd_bytes(outer, inner, C, n) bytes; its content before the call does not matter.  It holds the small
+ * per-sequence tables and the parameter-gradient partial sums of S = min(128, 256 / splits) sequence slots (splits = 1 .. 8, a
+ * function of n): sequences are worked in chunks of at most S and the chunks' tables are added in a fixed order (deterministic, no
+ * atomics; the token splits depend on n only, so a sequence's dx does not depend on what shares the call).  The size needs no
+ * device query and stops growing at outer * inner = S; it is at most 256 (514 C + 256) + 128 (768 C + 4480) + 256 C floats (62 MB at
+ * C = 64, 121 MB at C = 128).
+ * Checked before any launch or device query, each with its own message: SDC_ENULL for a null x, g_pre, wqkv, wo, dy, dx, dg, dwqkv,
+ * dwo or work, and for bo without dbo; SDC_EINVAL for a norm mode other than (0, -1), C not in {64, 128}, n % 64 != 0,
+ * outer * inner >= 65536, sc >= 2^27, a wqkv / wo not 16-byte aligned, or dx aliasing x or dy. */
+size_t sdc_linattn_block_bwd_bytes(int outer, int inner, int C, int64_t n);
+int sdc_linattn_block_bwd(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo, const float* dy,
+                          float* dx, float* dg, float* dwqkv, float* dwo, float* dbo, void* work, int outer, int inner, int C,
+                          int64_t n, int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream);
 size_t sdc_linattn_bwd_bytes(int outer, int inner, int heads, int64_t n);      /* scratch of sdc_linattn_bwd */
 int sdc_linattn_bwd(const float* qkv, const float* dout, float* dqkv, void* work, int outer, int inner, int heads, int64_t n,
                     int64_t q_so, int64_t q_sc, int64_t q_si, int64_t o_so, int64_t o_sc, int64_t o_si, void* stream);

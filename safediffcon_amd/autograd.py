@@ -116,6 +116,14 @@ def check_train_fuse_attn(v):
     return v
 
 
+def check_train_fuse_linattn(v):
+    """net.train_fuse_linattn: False (the chain of nodes, the default) or True (the fused SpatialLinearAttention node where it covers
+    the site); only booleans, anything else raises ValueError"""
+    if not isinstance(v, bool):
+        raise ValueError(f"train_fuse_linattn must be True or False (got {v!r})")
+    return v
+
+
 def f16_train_form(k, stride, pad, up):
     """the conv forms train_precision 6 / 7 route to the fp16 kernels: 1x1x3 / 1x3x3 / 3x3x3 taps, stride 1, pad 1 along every
     3-wide axis, no folded upsampling (the kernels' own coverage -- row widths, LDS -- is checked by the library)"""
@@ -462,6 +470,32 @@ class TemporalBlockFn(Function):
         return dx, dg.reshape(ctx.gshape), dwqkv_p.t().contiguous(), dwo_p.t().contiguous(), None, dbias
 
 
+class LinAttnBlockFn(Function):
+    """Residual(PreNorm(SpatialLinearAttention)) of the smoke net at width 64 / 128 as ONE node (net.train_fuse_linattn): forward
+    sdc_linattn_block_sel (impl 0, literal fp32), backward sdc_linattn_block_bwd.  Saved for backward: x and the parameters -- no
+    intermediate (the backward recomputes xn, q, k and the softmaxes from x).  wqkv (384, C, 1, 1) and wo (C, 128, 1, 1) are the
+    nn.Conv2d weights; the kernels read their transposes (the packed [C][384] / [128][C] tables, copied per call), and the weight
+    gradients come back in the parameters' own layouts."""
+
+    @staticmethod
+    def forward(ctx, x, g, wqkv, wo, bo):
+        gd = g.detach().reshape(-1).contiguous()
+        Cc = gd.numel()
+        wqkv_p, wo_p = wqkv.detach().reshape(3 * HID, Cc).t().contiguous(), wo.detach().reshape(Cc, HID).t().contiguous()
+        bd = None if bo is None else bo.detach().contiguous()
+        ctx.save_for_backward(x, gd, wqkv, wo, bd)
+        ctx.gshape = g.shape
+        return grad_ops.linattn_block(x, gd, wqkv_p, wo_p, bd)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gd, wqkv, wo, bd = ctx.saved_tensors
+        Cc = gd.numel()
+        wqkv_p, wo_p = wqkv.detach().reshape(3 * HID, Cc).t().contiguous(), wo.detach().reshape(Cc, HID).t().contiguous()
+        dx, dg, dwqkv_p, dwo_p, dbo = grad_ops.linattn_block_bwd(x, gd, wqkv_p, wo_p, bd, gy.contiguous())
+        return dx, dg.reshape(ctx.gshape), dwqkv_p.t().reshape(wqkv.shape), dwo_p.t().reshape(wo.shape), dbo
+
+
 class LinAttnCoreFn(Function):
     """linear attention core (sdc_linattn / sdc_linattn_bwd); geom = (heads, outer, inner, n, q strides, out strides, out shape)"""
 
@@ -509,12 +543,14 @@ class Trainer:
         self.arena = grad_ops.PackArena()
         self.tprec = None        # net.train_precision, read at the start of every training forward (step)
         self.fuse_attn = False   # net.train_fuse_attn, likewise
+        self.fuse_la = False     # net.train_fuse_linattn, likewise
 
     @contextlib.contextmanager
     def step(self, device):
         """one training forward: every packed conv weight refreshed by one launch, conv nodes bound to this net's arena"""
         self.tprec = check_train_precision(getattr(self.net, "train_precision", None))
         self.fuse_attn = check_train_fuse_attn(getattr(self.net, "train_fuse_attn", False))
+        self.fuse_la = check_train_fuse_linattn(getattr(self.net, "train_fuse_linattn", False))
         self.arena.begin(device)
         prev, _ARENA.cur = _ARENA.cur, self.arena
         try:
@@ -592,6 +628,10 @@ class Trainer:
         """Residual(PreNorm(SpatialLinearAttention)), per frame: conv3d.py:232-258"""
         B, Cc, Fr, H, W = x.shape
         hw = H * W
+        if (self.fuse_la and self.net.fuse_linattn and Cc in (64, 128) and hw % 64 == 0 and B * Fr < 65536 and x.is_contiguous()):
+            # the sites the sampler plans fuse (unet.py, _la_fusable): one node, nothing but x saved
+            return LinAttnBlockFn.apply(x, self.P(f"{p}.fn.norm.gamma"), self.P(f"{p}.fn.fn.to_qkv.weight"),
+                                        self.P(f"{p}.fn.fn.to_out.weight"), self.P(f"{p}.fn.fn.to_out.bias"))
         xn = ChanNormFn.apply(x, self.P(f"{p}.fn.norm.gamma"), 0)
         qkv = self._pw(f"{p}.fn.fn.to_qkv.weight", xn)
         o = LinAttnCoreFn.apply(qkv, (HEADS, B, Fr, hw, (3 * HID * Fr * hw, Fr * hw, hw), (HID * Fr * hw, Fr * hw, hw), (B, HID, Fr, H, W)))

@@ -435,6 +435,15 @@ extern "C" size_t sdc_linattn_block_bytes(int outer, int inner, int C, int64_t n
     return sizeof(float) * (size_t)(nseq * ns * 4 * 32 * (C + 2) + nseq * HID * C);
 }
 
+int sdc::la_launch_ctx(const LaArgs& a, int C, dim3 grid, hipStream_t stream) {
+    const size_t ldsb = sizeof(float) * (size_t)((C + HID) * XP + 8 * TT + 2 * C);
+    static std::atomic<uint64_t> attr{0};
+    SDC_LDS_OPTIN(attr, (la_blk_ctx<128, false>), 96 * 1024, "sdc_linattn_block_bwd");
+    if (C == 64) hipLaunchKernelGGL((la_blk_ctx<64, false>), grid, dim3(NT), ldsb, stream, a);
+    else hipLaunchKernelGGL((la_blk_ctx<128, false>), grid, dim3(NT), ldsb, stream, a);
+    return SDC_OK;
+}
+
 namespace {
 int linattn_block_impl(const float* x, const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_G,
                        const float* gn_res, const float* g_pre, const float* wqkv, const float* wo, const float* bo,

@@ -31,6 +31,9 @@ struct LaArgs {
 // sdc_linattn_block_sel / sdc_linattn_block_gn_sel (sdc_lablock.hip) around la_blk_mid: the grids and arguments of la_blk_ctx / la_blk_out
 int la_x3_launch_ctx(const LaArgs& a, int C, bool gn, dim3 grid, hipStream_t stream);
 int la_x3_launch_out(const LaArgs& a, int C, dim3 grid, hipStream_t stream);
+// pass 1 in fp32 (la_blk_ctx of sdc_lablock.hip, no GroupNorm on load) for the block's backward (sdc_lablock_bwd.hip), which re-runs
+// it into its own workspace: grid = (a.nsplit, sequences)
+int la_launch_ctx(const LaArgs& a, int C, dim3 grid, hipStream_t stream);
 
 }  // namespace sdc
 

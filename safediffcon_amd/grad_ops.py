@@ -231,6 +231,44 @@ def tattn_block_bwd(x, g, wqkv_p, wo_p, rot, bias, dy, eps=1e-5, work=None):
     return dx, dg, dwqkv, dwo, dbias
 
 
+def _linattn_geom(x):
+    B, Cc, Fr, H, W = x.shape
+    hw = H * W
+    return B, Fr, Cc, hw, Cc * Fr * hw, Fr * hw, hw
+
+
+def linattn_block(x, g, wqkv_p, wo_p, bo, eps=1e-5):
+    """the fused SpatialLinearAttention block in literal fp32 (sdc_linattn_block_sel, impl 0; channel LayerNorm in front, no norm
+    behind): x (B, C, F, H, W) contiguous, C in {64, 128}, H W % 64 == 0; g (C), wqkv_p packed [C][384], wo_p packed [128][C],
+    bo (C) or None -> y"""
+    _need_cuda(x, g, wqkv_p, wo_p, bo)
+    lib = _lib.get_lib()
+    geom = _linattn_geom(x)
+    y = torch.empty_like(x)
+    work = torch.empty(int(lib.sdc_linattn_block_bytes(geom[0], geom[1], geom[2], geom[3])) // 4, dtype=torch.float32, device=x.device)
+    check(lib.sdc_linattn_block_sel(x.data_ptr(), g.data_ptr(), wqkv_p.data_ptr(), wo_p.data_ptr(), 0 if bo is None else bo.data_ptr(), 0,
+                                    work.data_ptr(), y.data_ptr(), *geom, 0, -1, eps, 0, _stream(x)), "sdc_linattn_block_sel")
+    return y
+
+
+def linattn_block_bwd(x, g, wqkv_p, wo_p, bo, dy, eps=1e-5, work=None):
+    """backward of linattn_block from x and dy alone (sdc_linattn_block_bwd) -> (dx, dg, dwqkv_p, dwo_p, dbo | None); the gradients
+    of the weights come in the packed layouts of wqkv_p and wo_p"""
+    _need_cuda(x, g, wqkv_p, wo_p, bo, dy)
+    lib = _lib.get_lib()
+    geom = _linattn_geom(x)
+    dx, dg, dwqkv, dwo = torch.empty_like(x), torch.empty_like(g), torch.empty_like(wqkv_p), torch.empty_like(wo_p)
+    dbo = None if bo is None else torch.empty_like(bo)
+    if work is None:
+        work = torch.empty(int(lib.sdc_linattn_block_bwd_bytes(geom[0], geom[1], geom[2], geom[3])) // 4, dtype=torch.float32,
+                           device=x.device)
+    check(lib.sdc_linattn_block_bwd(x.data_ptr(), g.data_ptr(), wqkv_p.data_ptr(), wo_p.data_ptr(), 0 if bo is None else bo.data_ptr(),
+                                    dy.data_ptr(), dx.data_ptr(), dg.data_ptr(), dwqkv.data_ptr(), dwo.data_ptr(),
+                                    0 if dbo is None else dbo.data_ptr(), work.data_ptr(), *geom, 0, -1, eps, _stream(x)),
+          "sdc_linattn_block_bwd")
+    return dx, dg, dwqkv, dwo, dbo
+
+
 def linattn_core(qkv, out, heads, outer, inner, n, qs, os_):
     """linear attention core (sdc_linattn): strides (so, sc, si) of qkv and out"""
     lib = _lib.get_lib()

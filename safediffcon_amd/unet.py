@@ -315,6 +315,14 @@ class _HipUNet(nn.Module):
         # independent of train_precision.  Wider sites, the 1-D nets, net(x, t) and the samplers never see it; a live GraphedLossStep
         # keeps the mode it was captured with.  Only booleans are accepted (ValueError otherwise).
         self.train_fuse_attn = False
+        # the same for the smoke net's Residual(PreNorm(SpatialLinearAttention)) sites, read at every forward_train: False (default) =
+        # today's chain (norm -> 1x1 -> core -> 1x1 -> add), bit for bit; True (opt-in) = the sites the sampler plans fuse (width 64 /
+        # 128, H W % 64 == 0, B F < 65536, contiguous, fuse_linattn on) as ONE node: forward sdc_linattn_block_sel (impl 0, literal
+        # fp32), backward sdc_linattn_block_bwd, which recomputes everything from x and dy -- only x is saved instead of x, xn, qkv and
+        # the core's output.  fp32 in another summation order; independent of train_fuse_attn and train_precision.  Wider sites, the
+        # 1-D nets (their LinearAttention has a post norm), net(x, t) and the samplers never see it; a live GraphedLossStep keeps the
+        # mode it was captured with.  Only booleans are accepted (ValueError otherwise).
+        self.train_fuse_linattn = False
         # 7-tap stem conv (init_conv) of the sampler plans -- model(x, t), graph-replayed or eager, and the samplers -- on the fp16
         # matrix pipe (opt-in): fp16 operands rounded to nearest even, fp32 accumulation, where conv_stem_f16_kernel covers it
         # (Cin <= 8, Cout a multiple of 64, rows of 16 / 32 / 64 / 128: the smoke and Burgers stems at production width; the tokamak
@@ -414,6 +422,15 @@ class _HipUNet(nn.Module):
     def train_fuse_attn(self, v):
         from .autograd import check_train_fuse_attn
         self.__dict__["_train_fuse_attn"] = check_train_fuse_attn(v)
+
+    @property
+    def train_fuse_linattn(self):
+        return self.__dict__.get("_train_fuse_linattn", False)
+
+    @train_fuse_linattn.setter
+    def train_fuse_linattn(self, v):
+        from .autograd import check_train_fuse_linattn
+        self.__dict__["_train_fuse_linattn"] = check_train_fuse_linattn(v)
 
     def P(self, key):
         m = self

@@ -340,12 +340,21 @@ int sdc_tattn_block_f16(const float* x, const float* g_pre, const void* wpk, con
  * sdc_tattn_block_x3: arguments, strides, tables, checks and error codes of sdc_tattn_block_f16, all before any launch.  No atomics,
  * fixed accumulation order; a sample's output does not depend on the batch.
  * sdc_tattn_block_x3_ok: 1 where the routing table of net.attn_split lists the site -- (C, frames, inner = H * W), never B: the sizes
- * at which the kernel measured faster than sdc_tattn_block in every repeat. */
+ * at which the kernel measured faster than sdc_tattn_block in every repeat.
+ *
+ * sdc_tattn_block_x3_sel: the same arguments plus `impl` in front of the stream.  0 = every wave runs a head between the same two
+ * barriers; 1 = waves 4 - 7, the second wave of every SIMD, run half a head behind the first four ("The skewed
+ * form").  Same arithmetic, same bits.  Any other impl is SDC_EINVAL before any launch.
+ * sdc_tattn_block_x3_impl(C, frames, inner): the measured table of impl -- never keyed on B --: 1 at the sizes where impl 1 beat impl 0
+ * in every repeat at the bench batch, 0 everywhere else.  sdc_tattn_block_x3 is the _sel entry with that answer. */
 size_t sdc_pack_tattn_x3_bytes(void);
 int sdc_pack_tattn_x3(const float* wqkv, const float* wo, void* dst, void* stream);
 int sdc_tattn_block_x3(const float* x, const float* g_pre, const void* wpk, const float* rot, const float* bias, float* y,
                        int outer, int inner, int C, int ntok, int64_t so, int64_t sc, int64_t st, float eps, void* stream);
 int sdc_tattn_block_x3_ok(int C, int ntok, int inner);
+int sdc_tattn_block_x3_sel(const float* x, const float* g_pre, const void* wpk, const float* rot, const float* bias, float* y,
+                           int outer, int inner, int C, int ntok, int64_t so, int64_t sc, int64_t st, float eps, int impl, void* stream);
+int sdc_tattn_block_x3_impl(int C, int ntok, int inner);
 
 /* ------------------------------------------------------- softmax attention */
 /* Attention core (heads x 32): out = softmax(q*scale . k^T + bias) v, optional rotary on q,k.

@@ -118,6 +118,9 @@ SIGNATURES = {
     "sdc_tattn_block_x3": (C.c_int, [_f32p, _f32p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                      _i64, _i64, _i64, C.c_float, _stream]),
     "sdc_tattn_block_x3_ok": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "sdc_tattn_block_x3_sel": (C.c_int, [_f32p, _f32p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         _i64, _i64, _i64, C.c_float, C.c_int, _stream]),
+    "sdc_tattn_block_x3_impl": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "sdc_attn": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64,
                            _i64, _i64, _i64, _i64, _stream]),
     "sdc_act": (C.c_int, [_f32p, _f32p, _i64, C.c_int, _stream]),

@@ -60,6 +60,10 @@
       buffers, the medians of 20 launches in three interleaved repeats -- the data of the routing table (sdc_tattn_block_x3_ok, DESIGN
       section 19: a shape qualifies when every repeat beats every repeat of the fp32 kernel); then the C4 sampler step with the switch
       off against on
+  python tools/f16_step.py --attn-skew [--no-step]
+      the skewed form of that block (ta_block_x3s_kernel): sdc_tattn_block_x3_sel with impl 0 against impl 1 on the
+      same buffers at 64 x 64 (B = 64 and B = 2) and 32 x 32 (B = 64), the medians of 20 launches in three interleaved repeats; a size
+      qualifies for sdc_tattn_block_x3_impl when every repeat of impl 1 beats every repeat of impl 0 at the bench batch
 """
 import _libsel  # noqa: F401  (SDC_LIB_PATH -> safediffcon_amd._lib.use_library, tools only)
 import argparse
@@ -633,6 +637,64 @@ def attn_split_shapes():
         torch.cuda.empty_cache()
 
 
+def attn_skew_shapes():
+    """the skewed form of the bf16-split temporal-attention block (ta_block_x3s_kernel): sdc_tattn_block_x3_sel with impl 0 against impl
+    1 on the same buffers at 64 x 64 (the C4 site, B = 64 and B = 2) and 32 x 32 (B = 64); the medians of 20 launches, three
+    interleaved repeats; a size QUALIFIES for sdc_tattn_block_x3_impl when every repeat of impl 1 beats every repeat of impl 0 at the
+    bench batch"""
+    from safediffcon_amd.engine import pack_tattn_x3
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    torch.manual_seed(0)
+    wqkv, wo = torch.randn(384, 64, device=DEV) * 0.2, torch.randn(64, 128, device=DEV) * 0.1
+    g = torch.rand(64, device=DEV) + 0.5
+    ang = torch.arange(32, dtype=torch.float32)[:, None] * (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32)))[None, :]
+    rot = torch.stack((ang.cos(), ang.sin()), dim=-1).reshape(-1).to(DEV)
+    bias = torch.randn(4 * 32 * 32, device=DEV) * 0.3
+    wpk = pack_tattn_x3(wqkv, wo)
+    for B, hw in ((64, 64), (2, 64), (64, 32)):
+        x = torch.randn(B, 64, 32, hw, hw, device=DEV) * 0.5
+        y0, y1 = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
+        tail = (B, hw * hw, 64, 32, 64 * 32 * hw * hw, 32 * hw * hw, hw * hw, 1e-5)
+        a0 = (x.data_ptr(), g.data_ptr(), wpk.data_ptr(), rot.data_ptr(), bias.data_ptr(), y0.data_ptr(), *tail, 0)
+        a1 = (x.data_ptr(), g.data_ptr(), wpk.data_ptr(), rot.data_ptr(), bias.data_ptr(), y1.data_ptr(), *tail, 1)
+        m0, m1 = [], []
+        for _ in range(3):          # interleaved repeats of the median of 20: their spread is what a gain has to beat
+            m0.append(_time_call(lib.sdc_tattn_block_x3_sel, a0, stream))
+            m1.append(_time_call(lib.sdc_tattn_block_x3_sel, a1, stream))
+        med0, med1 = statistics.median(m0), statistics.median(m1)
+        listed = bool(lib.sdc_tattn_block_x3_impl(64, 32, hw * hw))
+        print(f"[measured] tattn x3 block B {B} 64 ch 32 frames {hw}x{hw} (inner {hw * hw}, {'listed' if listed else 'not listed'}): "
+              f"impl 0 (ta_block_x3_kernel) {' / '.join(f'{v * 1e3:.1f}' for v in m0)} us | impl 1 (ta_block_x3s_kernel) "
+              f"{' / '.join(f'{v * 1e3:.1f}' for v in m1)} us -> x{med0 / med1:.3f} "
+              f"{'QUALIFIES (every repeat beats every repeat)' if max(m1) < min(m0) else 'does NOT qualify'}; "
+              f"bit-identical: {bool(torch.equal(y0, y1))}", flush=True)
+        del x, y0, y1
+        torch.cuda.empty_cache()
+
+
+def attn_phase():
+    """one line of the phase account of ta_block_x3_kernel: the C4 site at B = 64, the median of 20 launches of impl
+    0, under an experiments build (python -m safediffcon_amd.build --experiments, SDC_LIB_PATH) with SDC_TAX3_DBG naming the part that
+    is switched off (1 LayerNorm, 2 y exit, 4 splits, 8 weight fetch and park, 16 fragment reads, 32 per-head barrier, 64 rotary and
+    softmax, 127 MFMAs only; 0 the whole kernel).  One process per value: the library reads the variable once.  WRONG RESULTS."""
+    from safediffcon_amd.engine import pack_tattn_x3
+    lib = _lib.get_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    torch.manual_seed(0)
+    wpk = pack_tattn_x3(torch.randn(384, 64, device=DEV) * 0.2, torch.randn(64, 128, device=DEV) * 0.1)
+    g = torch.rand(64, device=DEV) + 0.5
+    rot, bias = torch.rand(32 * 16 * 2, device=DEV), torch.randn(4 * 32 * 32, device=DEV) * 0.3
+    B, hw = 64, 64
+    x = torch.randn(B, 64, 32, hw, hw, device=DEV) * 0.5
+    y = torch.empty_like(x)
+    args = (x.data_ptr(), g.data_ptr(), wpk.data_ptr(), rot.data_ptr(), bias.data_ptr(), y.data_ptr(), B, hw * hw, 64, 32,
+            64 * 32 * hw * hw, 32 * hw * hw, hw * hw, 1e-5, 0)
+    ms = [_time_call(lib.sdc_tattn_block_x3_sel, args, stream) for _ in range(2)]
+    print(f"[measured] ta_block_x3_kernel B 64 64x64 SDC_TAX3_DBG={os.environ.get('SDC_TAX3_DBG', '0')} library "
+          f"{os.path.basename(os.environ.get('SDC_LIB_PATH', 'libsdc_hip.so'))}: {' / '.join(f'{v * 1e3:.1f}' for v in ms)} us", flush=True)
+
+
 def drift(T, stem=False, attn=False, linattn=False):
     torch.manual_seed(0)
     net = sdc.Unet3D_with_Conv3D(dim=64, dim_mults=(1, 2, 4), channels=7).to(DEV)
@@ -675,6 +737,8 @@ if __name__ == "__main__":
     ap.add_argument("--linattn", action="store_true", help="net.linattn_f16: the block launch at the C4 / C2 sites, the C4 and C2 steps (with --drift: 4 + linattn_f16 against 4)")
     ap.add_argument("--linattn-split", action="store_true", help="the fused LinearAttention block, impl 0 (fp32) against impl 1 (bf16-split q / k projections) launch by launch; then the C4 and C2 steps of this build (the A/B is by commit: SDC_LIB_PATH)")
     ap.add_argument("--attn-split", action="store_true", help="net.attn_split: the block launch at the sites of the dim-64 smoke net and the C4 step with the switch off / on")
+    ap.add_argument("--attn-skew", action="store_true", help="the bf16-split temporal-attention block, impl 0 against impl 1 (waves 4 - 7 half a head behind) launch by launch; then the C4 step of this build (the A/B is by commit: SDC_LIB_PATH)")
+    ap.add_argument("--attn-phase", action="store_true", help="one line of ta_block_x3_kernel's phase account: the C4 site under an experiments build with SDC_TAX3_DBG set")
     ap.add_argument("--no-step", action="store_true", help="--stem / --split / --gemm / --pw-split / --wino / --attn / --attn-split: the per-shape part only")
     a = ap.parse_args()
     wls = [w for w in a.workloads.split(",") if w]
@@ -697,6 +761,13 @@ if __name__ == "__main__":
                 step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=[4, "4+la", "6+stem+attn", "6+stem+attn+la"])
             if "c2" in wls:
                 step_ab(["c2"], a.steps, a.warmup, a.rounds, arms=[4, "4+la"])
+    elif a.attn_phase:
+        attn_phase()
+    elif a.attn_skew:
+        attn_skew_shapes()
+        if not a.no_step:
+            # the entry point carries no switch: the step's A/B is by commit (bench.py of the two checkouts, or SDC_LIB_PATH)
+            step_ab(["c4"], a.steps, a.warmup, a.rounds, arms=[4])
     elif a.attn_split:
         attn_split_shapes()
         if not a.no_step:

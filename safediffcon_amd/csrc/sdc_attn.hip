@@ -560,9 +560,9 @@ extern "C" int sdc_linattn(const float* qkv, float* ctx, float* out, int outer, 
     SDC_REQUIRE(outer > 0 && inner > 0 && heads > 0 && n > 0, SDC_EINVAL, "sdc_linattn: bad shape");
     const int64_t nblk = (int64_t)outer * inner * heads;
     SDC_REQUIRE(nblk < 65536 * 16, SDC_EINVAL, "sdc_linattn: too many sequences");
+    SDC_REQUIRE(nblk < 65536, SDC_EINVAL, "sdc_linattn: outer*inner*heads must be < 65536");      // (la_out_kernel's grid.y) before any launch
     hipStream_t s = sdc::as_stream(stream);
     hipLaunchKernelGGL(la_ctx_kernel, dim3((unsigned)nblk), dim3(NT), 0, s, qkv, ctx, inner, heads, n, q_so, q_sc, q_si);
-    SDC_REQUIRE(nblk < 65536, SDC_EINVAL, "sdc_linattn: outer*inner*heads must be < 65536");
     hipLaunchKernelGGL(la_out_kernel, dim3((unsigned)((n + NT - 1) / NT), (unsigned)nblk), dim3(NT), 0, s, qkv, ctx, out,
                        inner, heads, n, q_so, q_sc, q_si, o_so, o_sc, o_si);
     return sdc::check_launch("sdc_linattn");

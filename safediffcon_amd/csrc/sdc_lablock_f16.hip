@@ -192,9 +192,13 @@ __global__ __launch_bounds__(NT, (C == 64 ? 2 : 1)) void la16_ctx(const La16Args
             kacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, wk[s], kacc[1], 0, 0, 0);
         }
         // online softmax over tokens, per d, against an integer exponent
-        float tmax = kacc[0][0];
+        // (the first maximum in plain C++, as in la16_out: it reads the accumulators the last two MFMAs have just written, and
+        // behind la_max3's asm statement the compiler places no wait states -- at C = 64 the v_max3_f32 stood directly behind
+        // the MFMA and read a register that was stale or not with the load of the CU: run-to-run differences in the last bits
+        // once every CU was busy.  In front of the plain form it places them, and the rest of the chain depends on it.)
+        float tmax = fmaxf(kacc[0][0], kacc[1][0]);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) tmax = la_max3(tmax, kacc[0][r], kacc[1][r]);
+        for (int r = 1; r < 16; ++r) tmax = la_max3(tmax, kacc[0][r], kacc[1][r]);
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
         const float enew = fmaxf(erun, ceilf(tmax * LOG2E));
         const float f = pow2_neg(erun - enew);

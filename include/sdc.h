@@ -751,6 +751,28 @@ size_t sdc_linattn_block_bwd_bytes(int outer, int inner, int C, int64_t n);
 int sdc_linattn_block_bwd(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo, const float* dy,
                           float* dx, float* dg, float* dwqkv, float* dwo, float* dbo, void* work, int outer, int inner, int C,
                           int64_t n, int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream);
+
+/* The same for the post-norm form of the 1-D nets (LinearAttention of Unet2D / Unet1D): the backward of
+ * sdc_linattn_block_sel(..., impl = 0) with pre_mode in {0, 1} and post_mode in {0, 1} (0 channel LayerNorm, 1 RMSNorm; all four
+ * combinations),
+ *   y = x + N_post(Wo LA(N_pre(x)) + bo) g_post.
+ * Arguments, addressing, domain and contract are sdc_linattn_block_bwd's, plus g_post [C] and dg_post [C] (always required).  The
+ * post norm's backward turns every dy tile into dz = dL/d(Wo LA + bo) in the first sweep, which leaves it in dx's memory at the
+ * tile's own address; the second sweep reads it there before it overwrites the tile with dx (one owner per tile) -- still nothing
+ * of size C x tokens is written but dx.  At RMSNorm's clamp (||.|| <= 1e-12) the gradients are sdc_chan_norm_bwd's.
+ * work = sdc_linattn_block_post_bwd_bytes(outer, inner, C, n) bytes: sdc_linattn_block_bwd's tables plus T with its channel axis
+ * contiguous and the dg_post partials per sequence slot; no device query, stops growing at outer * inner = S; at most
+ * 256 (515 C + 256) + 128 (896 C + 4480) + 256 C floats (66 MB at C = 64, 129 MB at C = 128).
+ * Checked before any launch or device query, each with its own message: SDC_ENULL for a null x, g_pre, wqkv, wo, g_post, dy, dx,
+ * dg_pre, dwqkv, dwo, dg_post or work, and for bo without dbo; SDC_EINVAL for pre_mode not in {0, 1}, post_mode not in {0, 1}
+ * (-1 is sdc_linattn_block_bwd's form and the message says so), C not in {64, 128}, n % 64 != 0, outer * inner >= 65536,
+ * sc >= 2^27, wqkv or wo not 16-byte aligned, dx aliasing x or dy. */
+size_t sdc_linattn_block_post_bwd_bytes(int outer, int inner, int C, int64_t n);
+int sdc_linattn_block_post_bwd(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
+                               const float* g_post, const float* dy,
+                               float* dx, float* dg_pre, float* dwqkv, float* dwo, float* dbo, float* dg_post, void* work,
+                               int outer, int inner, int C, int64_t n, int64_t so, int64_t sc, int64_t si,
+                               int pre_mode, int post_mode, float eps, void* stream);
 size_t sdc_linattn_bwd_bytes(int outer, int inner, int heads, int64_t n);      /* scratch of sdc_linattn_bwd */
 int sdc_linattn_bwd(const float* qkv, const float* dout, float* dqkv, void* work, int outer, int inner, int heads, int64_t n,
                     int64_t q_so, int64_t q_sc, int64_t q_si, int64_t o_so, int64_t o_sc, int64_t o_si, void* stream);

@@ -175,6 +175,10 @@ SIGNATURES = {
     "sdc_linattn_block_bwd_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, _i64]),
     "sdc_linattn_block_bwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p,
                                         C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_float, _stream]),
+    "sdc_linattn_block_post_bwd_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, _i64]),
+    "sdc_linattn_block_post_bwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_float,
+                                             _stream]),
     "sdc_attn_bwd_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdc_attn_bwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _stream]),

@@ -496,6 +496,39 @@ class LinAttnBlockFn(Function):
         return dx, dg.reshape(ctx.gshape), dwqkv_p.t().reshape(wqkv.shape), dwo_p.t().reshape(wo.shape), dbo
 
 
+def la_post_fusable(B, Cc, n):
+    """the LinearAttention sites of the 1-D nets that net.train_fuse_linattn records as LinAttnPostBlockFn: the domain of
+    sdc_linattn_block_post_bwd less the one (width, tokens) pair whose fused forward + backward measured slower than the chain
+    (128 wide, 512 tokens: Unet2D(dim=64)'s ups.2.2 -- eight tiles in one token split, 64 workgroups at B = 64)"""
+    return Cc in (64, 128) and n % 64 == 0 and B < 65536 and (Cc, n) != (128, 512)
+
+
+class LinAttnPostBlockFn(Function):
+    """Residual(PreNorm(LinearAttention)) of the 1-D nets (Unet2D / Unet1D: a channel norm in front and one behind to_out, both of
+    the net's NORM_MODE) at width 64 / 128 as ONE node (net.train_fuse_linattn): forward sdc_linattn_block_sel (impl 0, literal
+    fp32), backward sdc_linattn_block_post_bwd.  Saved for backward: x and the parameters -- no intermediate.  wqkv (384, C, 1...)
+    and wo (C, 128, 1...) are the conv weights; the kernels read their transposes (the packed [C][384] / [128][C] tables, copied per
+    call), and the weight gradients come back in the parameters' own layouts."""
+
+    @staticmethod
+    def forward(ctx, x, g_pre, wqkv, wo, bo, g_post, mode):
+        gd, gpd = g_pre.detach().reshape(-1).contiguous(), g_post.detach().reshape(-1).contiguous()
+        Cc = gd.numel()
+        wqkv_p, wo_p = wqkv.detach().reshape(3 * HID, Cc).t().contiguous(), wo.detach().reshape(Cc, HID).t().contiguous()
+        bd = None if bo is None else bo.detach().contiguous()
+        ctx.save_for_backward(x, gd, wqkv, wo, bd, gpd)
+        ctx.mode, ctx.gshape, ctx.gpshape = mode, g_pre.shape, g_post.shape
+        return grad_ops.linattn_post_block(x, gd, wqkv_p, wo_p, bd, gpd, mode, mode)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gd, wqkv, wo, bd, gpd = ctx.saved_tensors
+        Cc = gd.numel()
+        wqkv_p, wo_p = wqkv.detach().reshape(3 * HID, Cc).t().contiguous(), wo.detach().reshape(Cc, HID).t().contiguous()
+        dx, dg, dwqkv_p, dwo_p, dbo, dgp = grad_ops.linattn_post_block_bwd(x, gd, wqkv_p, wo_p, bd, gpd, gy.contiguous(), ctx.mode, ctx.mode)
+        return dx, dg.reshape(ctx.gshape), dwqkv_p.t().reshape(wqkv.shape), dwo_p.t().reshape(wo.shape), dbo, dgp.reshape(ctx.gpshape), None
+
+
 class LinAttnCoreFn(Function):
     """linear attention core (sdc_linattn / sdc_linattn_bwd); geom = (heads, outer, inner, n, q strides, out strides, out shape)"""
 
@@ -609,6 +642,11 @@ class Trainer:
         """Residual(PreNorm(LinearAttention)): 1D/model/unet.py:182-222 (LayerNorm), tokamak/model/unet.py:182-222 (RMSNorm)"""
         B, Cc = x.shape[:2]
         n = x.numel() // (B * Cc)
+        if self.fuse_la and self.net.fuse_linattn and la_post_fusable(B, Cc, n) and x.is_contiguous():
+            # the sites the sampler plans fuse (unet.py, _lin_attn) but one: one node, nothing but x saved
+            return LinAttnPostBlockFn.apply(x, self.P(f"{p}.fn.norm.g"), self.P(f"{p}.fn.fn.to_qkv.weight"),
+                                            self.P(f"{p}.fn.fn.to_out.0.weight"), self.P(f"{p}.fn.fn.to_out.0.bias"),
+                                            self.P(f"{p}.fn.fn.to_out.1.g"), mode)
         xn = ChanNormFn.apply(x, self.P(f"{p}.fn.norm.g"), mode)
         qkv = self._pw(f"{p}.fn.fn.to_qkv.weight", xn)
         o = LinAttnCoreFn.apply(qkv, (HEADS, B, 1, n, (3 * HID * n, n, 0), (HID * n, n, 0), (B, HID, *x.shape[2:])))

@@ -18,6 +18,10 @@
 //   5. lab_dx    : x, dy tile -> xn, s, p -> dq~ = T^T dy, dQ, dp = U xn, dK -> dxn = Wq^T dQ + Wk^T dK + U^T p -> LayerNorm
 //                  backward + residual -> dx;  dWq, dWk, dgamma partials per (sequence, split)
 //   6. lab_sum   : the partial tables in a fixed order (the first chunk overwrites the outputs, later chunks add to them)
+// The post-norm form of the 1-D nets (sdc_linattn_block_post_bwd), y = x + N_post(Wo . LA(N_pre(x)) + bo) g_post
+// with N in {channel LayerNorm, RMSNorm}, runs the same launches with the POST instantiations of the two sweeps: lab_dt also forms
+// z = T q~ + bo, the post norm's backward dz and dg_post, uses dz for dy and leaves the dz tile in dx's memory; lab_dx reads it there
+// in dy's place and adds dy itself only as the residual.
 // All matrix products are v_mfma_f32_32x32x2_f32.  No atomics; every partial has one owner and is written in full; the token splits
 // are pick_nsplit's (a function of the sequence length only), so a sequence's dx does not depend on what shares the launch.
 #include "sdc_common.h"
@@ -48,10 +52,12 @@ struct LabWs {
     int64_t tabv;       // [C][128]                 dWv of the slot's sequences
     int64_t tabo;       // [128][C]                 dWo
     int64_t wt;         // [256 hd][C]              Wq | Wk with c contiguous (one copy per call)
+    int64_t tt;         // [128 hd][C co]           T with co contiguous        (post-norm form only)
+    int64_t dgpp;       // [ns][C]                  dg_post partials            (post-norm form only)
     int64_t total;
 };
 
-inline LabWs lab_layout(int C, int ns, int nslot) {
+inline LabWs lab_layout(int C, int ns, int nslot, bool post = false) {
     LabWs L;
     int64_t o = 0;
     const int64_t s = nslot;
@@ -69,6 +75,8 @@ inline LabWs lab_layout(int C, int ns, int nslot) {
     L.tabv = o;  o += s * C * HID;
     L.tabo = o;  o += s * HID * C;
     L.wt = o;    o += 256 * C;
+    L.tt = o;    if (post) o += s * HID * C;
+    L.dgpp = o;  if (post) o += s * ns * C;
     L.total = o;
     return L;
 }
@@ -76,8 +84,10 @@ inline LabWs lab_layout(int C, int ns, int nslot) {
 struct LabArgs {
     const float* x; const float* dy; const float* g; const float* wqkv; const float* wo;
     float* dx; float* ws;
+    const float* bo; const float* gp;               // post-norm form: the output bias (or null) and the post norm's gain
     LabWs L;
     int inner, ns0, nsplit, tiles_per_split, ntiles;
+    int pre_mode, post_mode;                        // 0 LayerNorm, 1 RMSNorm; post_mode -1: no post norm
     float eps;
     int64_t so, sc, si;
 };
@@ -87,25 +97,40 @@ __global__ __launch_bounds__(NT) void lab_wt_kernel(const float* __restrict__ wq
     wt[(int64_t)threadIdx.x * C + blockIdx.x] = wqkv[(int64_t)blockIdx.x * (3 * HID) + threadIdx.x];
 }
 
-// channel LayerNorm of a tile as norm_tile (sdc_lablock.hip) has it: xs[c][tok] = xh * g; v becomes xh; returns rstd
+// channel norm of a tile as norm_tile (sdc_lablock.hip) has it: xs[c][tok] = xh * g; v becomes xh; returns the factor xh was scaled
+// by: rstd (mode 0, LayerNorm: xh = (x - mean) rstd) or sqrt(C) / max(||x||, 1e-12) (mode 1, RMSNorm: xh = x f).  `live` is 0 where
+// mode 1's clamp holds (the backward then drops the term through the norm, as sdc_chan_norm_bwd does) and 1 everywhere else.
 template <int C>
-__device__ __forceinline__ float ln_tile(float (&v)[C / 4], const float* __restrict__ g, float eps, float* __restrict__ xs,
-                                         float* __restrict__ red, int tid) {
+__device__ __forceinline__ float ln_tile(float (&v)[C / 4], const float* __restrict__ g, int mode, float eps, float* __restrict__ xs,
+                                         float* __restrict__ red, int tid, float& live) {
     constexpr int CG = C / 4;
     const int tok = tid & 63, grp = tid >> 6;
-    float s = 0.f;
+    float rstd;
+    live = 1.f;
+    if (mode == 0) {
+        float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < CG; ++k) s += v[k];
-    red[grp * TT + tok] = s;
-    __syncthreads();
-    const float mean = (red[tok] + red[TT + tok] + red[2 * TT + tok] + red[3 * TT + tok]) * (1.0f / C);
-    float q = 0.f;
+        for (int k = 0; k < CG; ++k) s += v[k];
+        red[grp * TT + tok] = s;
+        __syncthreads();
+        const float mean = (red[tok] + red[TT + tok] + red[2 * TT + tok] + red[3 * TT + tok]) * (1.0f / C);
+        float q = 0.f;
 #pragma unroll
-    for (int k = 0; k < CG; ++k) { v[k] -= mean; q += v[k] * v[k]; }
-    red[(4 + grp) * TT + tok] = q;
-    __syncthreads();
-    const float var = (red[4 * TT + tok] + red[5 * TT + tok] + red[6 * TT + tok] + red[7 * TT + tok]) * (1.0f / C);
-    const float rstd = rsqrtf(var + eps);
+        for (int k = 0; k < CG; ++k) { v[k] -= mean; q += v[k] * v[k]; }
+        red[(4 + grp) * TT + tok] = q;
+        __syncthreads();
+        const float var = (red[4 * TT + tok] + red[5 * TT + tok] + red[6 * TT + tok] + red[7 * TT + tok]) * (1.0f / C);
+        rstd = rsqrtf(var + eps);
+    } else {
+        float q = 0.f;
+#pragma unroll
+        for (int k = 0; k < CG; ++k) q += v[k] * v[k];
+        red[grp * TT + tok] = q;
+        __syncthreads();
+        const float nrm = sqrtf(red[tok] + red[TT + tok] + red[2 * TT + tok] + red[3 * TT + tok]);
+        rstd = sqrtf((float)C) / fmaxf(nrm, 1e-12f);
+        live = nrm > 1e-12f ? 1.f : 0.f;
+    }
 #pragma unroll
     for (int k = 0; k < CG; ++k) {
         v[k] *= rstd;
@@ -113,6 +138,62 @@ __device__ __forceinline__ float ln_tile(float (&v)[C / 4], const float* __restr
     }
     __syncthreads();
     return rstd;
+}
+
+// Backward of the post norm on a tile (post-norm form, sweep 1).  zs[c][tok] holds z = T q~ + bo; gy the dy values of this thread's
+// (channel group, token) and becomes dz; dgp gathers dg_post = sum dy u.  With u = N(z) and du = dy g_post:
+//   mode 0: dz = rstd (du - mean_c du - u mean_c(du u));   mode 1: dz = f (du - u mean_c(du u)), f = sqrt(C) / max(||z||, 1e-12), the
+//   second term dropped where the clamp holds (sdc_chan_norm_bwd).
+// red: 12 rows; rows 0 - 7 are ln_tile's (free here: its last read lies behind a barrier), 8 - 11 take the third pair of sums.
+template <int C>
+__device__ __forceinline__ void post_bwd_tile(const float* __restrict__ zs, float (&gy)[C / 4], float (&dgp)[C / 4],
+                                              const float* __restrict__ gp, int mode, float eps, float* __restrict__ red, int tid) {
+    constexpr int CG = C / 4;
+    const int tok = tid & 63, grp = tid >> 6;
+    float u[CG];
+#pragma unroll
+    for (int k = 0; k < CG; ++k) u[k] = zs[(grp * CG + k) * XP + tok];
+    float f, live = 1.f;
+    if (mode == 0) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < CG; ++k) s += u[k];
+        red[grp * TT + tok] = s;
+        __syncthreads();
+        const float mean = (red[tok] + red[TT + tok] + red[2 * TT + tok] + red[3 * TT + tok]) * (1.0f / C);
+        float q = 0.f;
+#pragma unroll
+        for (int k = 0; k < CG; ++k) { u[k] -= mean; q += u[k] * u[k]; }
+        red[(4 + grp) * TT + tok] = q;
+        __syncthreads();
+        const float var = (red[4 * TT + tok] + red[5 * TT + tok] + red[6 * TT + tok] + red[7 * TT + tok]) * (1.0f / C);
+        f = rsqrtf(var + eps);
+    } else {
+        float q = 0.f;
+#pragma unroll
+        for (int k = 0; k < CG; ++k) q += u[k] * u[k];
+        red[(4 + grp) * TT + tok] = q;
+        __syncthreads();
+        const float nrm = sqrtf(red[4 * TT + tok] + red[5 * TT + tok] + red[6 * TT + tok] + red[7 * TT + tok]);
+        f = sqrtf((float)C) / fmaxf(nrm, 1e-12f);
+        live = nrm > 1e-12f ? 1.f : 0.f;
+    }
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < CG; ++k) {
+        u[k] *= f;
+        dgp[k] += gy[k] * u[k];
+        gy[k] *= gp[grp * CG + k];                  // du
+        s1 += gy[k];
+        s2 += gy[k] * u[k];
+    }
+    red[grp * TT + tok] = s1;                       // (rows 0 - 3: every thread read them before the barrier above)
+    red[(8 + grp) * TT + tok] = s2;
+    __syncthreads();
+    const float m1 = mode == 0 ? ((red[tok] + red[TT + tok]) + (red[2 * TT + tok] + red[3 * TT + tok])) * (1.0f / C) : 0.f;
+    const float m2 = ((red[8 * TT + tok] + red[9 * TT + tok]) + (red[10 * TT + tok] + red[11 * TT + tok])) * (1.0f / C) * live;
+#pragma unroll
+    for (int k = 0; k < CG; ++k) gy[k] = f * (gy[k] - m1 - u[k] * m2);
 }
 
 // acc[j][r] = (W xn)[d = crow(r, lh)][tok = j*32 + l31], W[d][c] = wp[c * 384 + d]: wp points at column (head*32 + l31) of row lh
@@ -205,18 +286,25 @@ __global__ __launch_bounds__(NT) void lab_mid1_kernel(const LabArgs a) {
         for (int ks = 0; ks < 16; ++ks) { const int k = 2 * ks + lh; acc = MFMA(a.wo[(head * 32 + k) * C + rt * 32 + l31], cs[l31][k], acc); }
 #pragma unroll
         for (int r = 0; r < 16; ++r) tq[(rt * 32 + crow(r, lh)) * 32 + l31] = acc[r];
+        if (a.post_mode >= 0) {                     // the post-norm form's sweep 1 forms z = T q~ with co on the lanes
+            float* tt = a.ws + a.L.tt + slot * (HID * C) + (head * 32 + l31) * C + rt * 32;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tt[crow(r, lh)] = acc[r];
+        }
     }
 }
 
 // ------------------------------------------------------------------ sweep 1: dT and dbo partials per (split, sequence); wave = head
-template <int C>
+// POST (the post-norm form): z = T q~ + bo goes over xn once every wave has projected, the post norm's backward turns the dy tile
+// into dz, which takes dy's place in the products below and is left in dx's memory at the tile's own address for sweep 2
+template <int C, bool POST>
 __global__ __launch_bounds__(NT) void lab_dt_kernel(const LabArgs a) {
     constexpr int NCT = C / 32, CG = C / 4;
     extern __shared__ float lds[];
-    float* const xs = lds;                          // [C][XP]   xn
-    float* const dys = xs + C * XP;                 // [C][XP]   dy
+    float* const xs = lds;                          // [C][XP]   xn; POST: then z
+    float* const dys = xs + C * XP;                 // [C][XP]   dy; POST: dz
     float* const qs = dys + C * XP;                 // [128][XP] q~
-    float* const red = qs + HID * XP;               // [8][TT]
+    float* const red = qs + HID * XP;               // [8][TT]; POST: [12][TT]
     const int tid = threadIdx.x, lane = tid & 63, head = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int tok = tid & 63, grp = tid >> 6;
     const int split = blockIdx.x;
@@ -232,6 +320,12 @@ __global__ __launch_bounds__(NT) void lab_dt_kernel(const LabArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) dt[t][r] = 0.f;
     float dbacc = 0.f;                              // channel tid (< C)
+    float dgp[POST ? CG : 1];                       // POST: dg_post of channel grp*CG + k over this lane's tokens
+#pragma unroll
+    for (int k = 0; k < (POST ? CG : 1); ++k) dgp[k] = 0.f;
+    const int pre = POST ? a.pre_mode : 0;
+    const int zrt = (NCT == 2) ? (head & 1) : head; // POST: this wave's row tile of z and its first column tile (as lab_dx's dxn)
+    const int zct0 = (NCT == 2) ? (head >> 1) : 0;
 
     const int t0 = split * a.tiles_per_split;
     const int t1 = min(t0 + a.tiles_per_split, a.ntiles);
@@ -239,9 +333,12 @@ __global__ __launch_bounds__(NT) void lab_dt_kernel(const LabArgs a) {
         float xv[CG], gy[CG];
         fetch_tile<C>(xseq + (int64_t)tile * TT, a.sc, tid, xv);
         fetch_tile<C>(dyseq + (int64_t)tile * TT, a.sc, tid, gy);
+        if constexpr (!POST) {
 #pragma unroll
-        for (int k = 0; k < CG; ++k) dys[(grp * CG + k) * XP + tok] = gy[k];
-        ln_tile<C>(xv, a.g, a.eps, xs, red, tid);
+            for (int k = 0; k < CG; ++k) dys[(grp * CG + k) * XP + tok] = gy[k];
+        }
+        float live;
+        ln_tile<C>(xv, a.g, pre, a.eps, xs, red, tid, live);
         f32x16 q[2];
         project<C>(wq, xs, l31, lh, q);
 #pragma unroll
@@ -251,7 +348,43 @@ __global__ __launch_bounds__(NT) void lab_dt_kernel(const LabArgs a) {
             for (int r = 0; r < 16; ++r) qs[(head * 32 + crow(r, lh)) * XP + j * 32 + l31] = q[j][r] * SCALE;
         }
         __syncthreads();
-        // dT^T[hd][co] += sum_tok q~[hd][tok] dy[co][tok]
+        if constexpr (POST) {
+            // z[co][tok] = bo[co] + sum_hd T[co][hd] q~[hd][tok]: NCT x 2 tiles of 32 x 32 over 4 waves, T's fragments from L2
+            constexpr int TPW = NCT / 2;
+            f32x16 z[TPW];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float b = a.bo ? a.bo[zrt * 32 + crow(r, lh)] : 0.f;
+#pragma unroll
+                for (int u = 0; u < TPW; ++u) z[u][r] = b;
+            }
+            const float* tt = a.ws + a.L.tt + slot * (HID * C) + zrt * 32 + l31;
+#pragma unroll 4
+            for (int ks = 0; ks < HID / 2; ++ks) {
+                const int k = 2 * ks + lh;
+                const float ta = tt[k * C];
+#pragma unroll
+                for (int u = 0; u < TPW; ++u) z[u] = MFMA(ta, qs[k * XP + (zct0 + u) * 32 + l31], z[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < TPW; ++u)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) xs[(zrt * 32 + crow(r, lh)) * XP + (zct0 + u) * 32 + l31] = z[u][r];
+            __syncthreads();
+            post_bwd_tile<C>(xs, gy, dgp, a.gp, a.post_mode, a.eps, red, tid);       // gy = dz from here on
+            la_gptr dp_ = la_uni(a.dx + o * a.so + i * a.si + (int64_t)tile * TT + (int64_t)(__builtin_amdgcn_readfirstlane(grp) * CG) * a.sc);
+            uint32_t off = (uint32_t)tok * 4u;
+#pragma unroll
+            for (int k = 0; k < CG; ++k) {
+                dys[(grp * CG + k) * XP + tok] = gy[k];
+                asm volatile("" : "+v"(off));
+                la_st(dp_, off, gy[k]);
+                dp_ += a.sc;
+                asm volatile("" : "+s"(dp_));
+            }
+            __syncthreads();
+        }
+        // dT^T[hd][co] += sum_tok q~[hd][tok] dy[co][tok]      (POST: dz)
 #pragma unroll 4
         for (int s = 0; s < TT / 2; ++s) {
             const int tk = 2 * s + lh;
@@ -272,6 +405,16 @@ __global__ __launch_bounds__(NT) void lab_dt_kernel(const LabArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) dtp[(head * 32 + crow(r, lh)) * C + t * 32 + l31] = dt[t][r];
     if (tid < C) a.ws[a.L.dbop + (slot * a.ns0 + split) * C + tid] = dbacc;
+    if constexpr (POST) {                           // (the tile loop ended on a barrier: xs is free)
+#pragma unroll
+        for (int k = 0; k < CG; ++k) xs[(grp * CG + k) * XP + tok] = dgp[k];
+        __syncthreads();
+        if (tid < C) {
+            float s = 0.f;
+            for (int t = 0; t < TT; ++t) s += xs[tid * XP + t];
+            a.ws[a.L.dgpp + (slot * a.ns0 + split) * C + tid] = s;
+        }
+    }
 }
 
 // ------------------------------------------------------------------ mid 2: per (head, sequence slot)
@@ -345,7 +488,9 @@ __global__ __launch_bounds__(NT) void lab_mid2_kernel(const LabArgs a) {
 }
 
 // ------------------------------------------------------------------ sweep 2: dx; dWq, dWk, dgamma partials per (split, sequence)
-template <int C>
+// POST (the post-norm form): the tile sweep 1 left in dx (dz) takes dy's place in the products; dy itself only enters the residual.
+// One workgroup owns a tile of dx, and each thread reads exactly the elements it overwrites at the end of the tile.
+template <int C, bool POST>
 __global__ __launch_bounds__(NT) void lab_dx_kernel(const LabArgs a) {
     constexpr int NCT = C / 32, CG = C / 4;
     constexpr int TPW = NCT / 2;                    // dxn tiles per wave (one row tile, TPW column tiles)
@@ -389,6 +534,7 @@ __global__ __launch_bounds__(NT) void lab_dx_kernel(const LabArgs a) {
     float dgacc[CG];
 #pragma unroll
     for (int k = 0; k < CG; ++k) dgacc[k] = 0.f;
+    const int pre = POST ? a.pre_mode : 0;
     __syncthreads();                                // st
 
     const int t0 = split * a.tiles_per_split;
@@ -396,10 +542,12 @@ __global__ __launch_bounds__(NT) void lab_dx_kernel(const LabArgs a) {
     for (int tile = t0; tile < t1; ++tile) {
         float xv[CG], gy[CG];
         fetch_tile<C>(xseq + (int64_t)tile * TT, a.sc, tid, xv);
-        fetch_tile<C>(dyseq + (int64_t)tile * TT, a.sc, tid, gy);
+        fetch_tile<C>((POST ? dxseq : dyseq) + (int64_t)tile * TT, a.sc, tid, gy);
 #pragma unroll
         for (int k = 0; k < CG; ++k) dys[(grp * CG + k) * XP + tok] = gy[k];
-        const float rstd = ln_tile<C>(xv, a.g, a.eps, xs, red, tid);        // xv = xh from here on
+        if constexpr (POST) fetch_tile<C>(dyseq + (int64_t)tile * TT, a.sc, tid, gy);      // the residual's dy, under the products
+        float live;
+        const float rstd = ln_tile<C>(xv, a.g, pre, a.eps, xs, red, tid, live);            // xv = xh from here on
         {   // s, dq~ = T_h^T dy, dQ = s (scale dq~ - sum_d s scale dq~)
             f32x16 q[2], dq[2];
             project<C>(wq, xs, l31, lh, q);
@@ -491,6 +639,7 @@ __global__ __launch_bounds__(NT) void lab_dx_kernel(const LabArgs a) {
             for (int r = 0; r < 16; ++r) gq[(rt * 32 + crow(r, lh)) * XP + (ct0 + u) * 32 + l31] = dxa[u][r];
         __syncthreads();
         // LayerNorm backward + the residual: dx = dy + rstd (g dxn - mean_c(g dxn) - xh mean_c(g dxn xh)); dgamma += dxn xh
+        // (RMSNorm, pre_mode 1: no mean term, and no xh term where the norm's clamp holds)
         float gd[CG];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -504,8 +653,9 @@ __global__ __launch_bounds__(NT) void lab_dx_kernel(const LabArgs a) {
         red[grp * TT + tok] = s1;
         red[(4 + grp) * TT + tok] = s2;
         __syncthreads();
-        const float m1 = ((red[tok] + red[TT + tok]) + (red[2 * TT + tok] + red[3 * TT + tok])) * (1.0f / C);
-        const float m2 = ((red[4 * TT + tok] + red[5 * TT + tok]) + (red[6 * TT + tok] + red[7 * TT + tok])) * (1.0f / C);
+        float m1 = ((red[tok] + red[TT + tok]) + (red[2 * TT + tok] + red[3 * TT + tok])) * (1.0f / C);
+        float m2 = ((red[4 * TT + tok] + red[5 * TT + tok]) + (red[6 * TT + tok] + red[7 * TT + tok])) * (1.0f / C);
+        if (pre != 0) { m1 = 0.f; m2 *= live; }
         {
             la_gptr dp_ = la_uni(dxseq + (int64_t)tile * TT + (int64_t)(__builtin_amdgcn_readfirstlane(grp) * CG) * a.sc);
             uint32_t off = (uint32_t)tok * 4u;
@@ -541,15 +691,15 @@ __global__ __launch_bounds__(NT) void lab_dx_kernel(const LabArgs a) {
 // ------------------------------------------------------------------ the partial tables of a chunk, in a fixed order
 // 64 output elements x SR_G groups per block (the scheme of tab_sum_kernel, sdc_tablock_bwd.hip): group g adds the tables k = g (mod
 // SR_G) in rising order, group 0 then adds the SR_G sums in order.  Tables per element: (slot, split) for dWq | dWk, dgamma and dbo,
-// slot for dWv and dWo.
+// slot for dWv and dWo.  The post-norm form adds C elements (dg_post, tables per (slot, split)) and C / 64 blocks.
 constexpr int SR_G = 16;
 __global__ __launch_bounds__(64 * SR_G) void lab_sum_kernel(const float* __restrict__ ws, const LabWs L, int C, int ns0, int nsplit,
                                                            int nslot, int accum, float* __restrict__ dwqkv, float* __restrict__ dwo,
-                                                           float* __restrict__ dg, float* __restrict__ dbo) {
+                                                           float* __restrict__ dg, float* __restrict__ dbo, float* __restrict__ dgp) {
     __shared__ float sh[SR_G][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int e = blockIdx.x * 64 + lane;           // the outputs are a multiple of 64 (514 C)
-    const int n0 = C * 3 * HID, n1 = n0 + HID * C, n2 = n1 + C;
+    const int n0 = C * 3 * HID, n1 = n0 + HID * C, n2 = n1 + C, n3 = n2 + C;
     const float* base;                              // element of table (slot 0, split 0)
     int64_t slot_stride, split_stride = 0;
     float* out;
@@ -562,8 +712,10 @@ __global__ __launch_bounds__(64 * SR_G) void lab_sum_kernel(const float* __restr
         out = dwo + (e - n0); base = ws + L.tabo + (e - n0); slot_stride = HID * C;
     } else if (e < n2) {
         out = dg + (e - n1); base = ws + L.tabqk + C * 256 + (e - n1); split_stride = C * 257; slot_stride = (int64_t)ns0 * split_stride;
-    } else {
+    } else if (e < n3) {
         out = dbo ? dbo + (e - n2) : nullptr; base = ws + L.dbop + (e - n2); split_stride = C; slot_stride = (int64_t)ns0 * C;
+    } else {
+        out = dgp + (e - n3); base = ws + L.dgpp + (e - n3); split_stride = C; slot_stride = (int64_t)ns0 * C;
     }
     const int per = split_stride ? nsplit : 1, K = nslot * per;
     float s = 0.f;
@@ -581,35 +733,91 @@ __global__ __launch_bounds__(64 * SR_G) void lab_sum_kernel(const float* __restr
     }
 }
 
-template <int C>
-int lab_chunk(LabArgs a, LaArgs f, int cnt, int accum, float* dwqkv, float* dwo, float* dg, float* dbo, hipStream_t s) {
-    constexpr size_t lds1 = sizeof(float) * (size_t)(2 * C * XP + HID * XP + 8 * TT);
+template <int C, bool POST>
+int lab_chunk(LabArgs a, LaArgs f, int cnt, int accum, float* dwqkv, float* dwo, float* dg, float* dbo, float* dgp, const char* what,
+              hipStream_t s) {
+    constexpr size_t lds1 = sizeof(float) * (size_t)(2 * C * XP + HID * XP + (POST ? 12 : 8) * TT);
     constexpr size_t lds2 = sizeof(float) * (size_t)(2 * C * XP + (C == 128 ? 2 : 3) * HID * XP + 8 * TT + 3 * HID);
     static_assert(lds1 <= 160 * 1024 && lds2 <= 160 * 1024, "LDS budget");
     static std::atomic<uint64_t> attr1{0}, attr2{0};
-    SDC_LDS_OPTIN(attr1, lab_dt_kernel<C>, 160 * 1024, "sdc_linattn_block_bwd");
-    SDC_LDS_OPTIN(attr2, lab_dx_kernel<C>, 160 * 1024, "sdc_linattn_block_bwd");
+    SDC_LDS_OPTIN(attr1, (lab_dt_kernel<C, POST>), 160 * 1024, what);
+    SDC_LDS_OPTIN(attr2, (lab_dx_kernel<C, POST>), 160 * 1024, what);
     const dim3 gs((unsigned)a.nsplit, (unsigned)cnt), gm(4, (unsigned)cnt);
     if (const int rc = sdc::la_launch_ctx(f, C, gs, s)) return rc;
     hipLaunchKernelGGL(lab_mid1_kernel<C>, gm, dim3(NT), 0, s, a);
-    hipLaunchKernelGGL(lab_dt_kernel<C>, gs, dim3(NT), lds1, s, a);
+    hipLaunchKernelGGL((lab_dt_kernel<C, POST>), gs, dim3(NT), lds1, s, a);
     hipLaunchKernelGGL(lab_mid2_kernel<C>, gm, dim3(NT), 0, s, a);
-    hipLaunchKernelGGL(lab_dx_kernel<C>, gs, dim3(NT), lds2, s, a);
-    static_assert((C * 3 * HID + HID * C + 2 * C) % 64 == 0, "lab_sum_kernel walks whole groups of 64");
-    hipLaunchKernelGGL(lab_sum_kernel, dim3((C * 3 * HID + HID * C + 2 * C) / 64), dim3(64 * SR_G), 0, s, (const float*)a.ws, a.L, C, a.ns0, a.nsplit, cnt, accum,
-                       dwqkv, dwo, dg, dbo);
+    hipLaunchKernelGGL((lab_dx_kernel<C, POST>), gs, dim3(NT), lds2, s, a);
+    constexpr int NOUT = C * 3 * HID + HID * C + (POST ? 3 : 2) * C;
+    static_assert(NOUT % 64 == 0, "lab_sum_kernel walks whole groups of 64");
+    hipLaunchKernelGGL(lab_sum_kernel, dim3(NOUT / 64), dim3(64 * SR_G), 0, s, (const float*)a.ws, a.L, C, a.ns0, a.nsplit, cnt, accum,
+                       dwqkv, dwo, dg, dbo, dgp);
     return SDC_OK;
 }
 
-}  // namespace
+// the launches of both entries (arguments checked by the caller): g_post / dg_post null and post_mode -1 for the form without a post norm
+int lab_backward(const char* what, const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
+                 const float* g_post, const float* dy, float* dx, float* dg, float* dwqkv, float* dwo, float* dbo, float* dg_post,
+                 void* work, int outer, int inner, int C, int64_t n, int64_t so, int64_t sc, int64_t si, int pre_mode, int post_mode,
+                 float eps, void* stream) {
+    const bool post = post_mode >= 0;
+    const int64_t nseq = (int64_t)outer * inner;
+    LabArgs a;
+    a.x = x; a.dy = dy; a.g = g_pre; a.wqkv = wqkv; a.wo = wo; a.dx = dx; a.ws = static_cast<float*>(work);
+    a.bo = bo; a.gp = g_post; a.pre_mode = pre_mode; a.post_mode = post_mode;
+    a.ntiles = (int)(n / TT);
+    a.ns0 = pick_nsplit(nseq, a.ntiles);
+    a.tiles_per_split = (a.ntiles + a.ns0 - 1) / a.ns0;
+    a.nsplit = (a.ntiles + a.tiles_per_split - 1) / a.tiles_per_split;      // no empty splits (as the forward)
+    const int SG = lab_slots(a.ns0);
+    a.L = lab_layout(C, a.ns0, (int)(nseq < SG ? nseq : SG), post);
+    a.inner = inner; a.eps = eps; a.so = so; a.sc = sc; a.si = si;
+    LaArgs f{};
+    f.g_pre = g_pre; f.wqkv = wqkv; f.wo = wo; f.part = a.ws + a.L.part;
+    f.nsplit = a.nsplit; f.tiles_per_split = a.tiles_per_split; f.ntiles = a.ntiles; f.tiles_per_blk = 1;
+    f.pre_mode = pre_mode; f.post_mode = -1; f.eps = eps; f.so = so; f.sc = sc; f.si = si;
+    hipStream_t s = sdc::as_stream(stream);
+    hipLaunchKernelGGL(lab_wt_kernel, dim3(C), dim3(NT), 0, s, wqkv, a.ws + a.L.wt, C);
+    // chunks of at most SG sequences: whole outer indices while they fit, else runs of one outer index's sequences
+    int accum = 0;
+    auto chunk = [&](int64_t off, int cinner, int cnt) -> int {
+        a.x = x + off; a.dy = dy + off; a.dx = dx + off; a.inner = cinner;
+        f.x = a.x; f.inner = cinner;
+        float* db = bo ? dbo : nullptr;
+        const int rc = post ? (C == 64 ? lab_chunk<64, true>(a, f, cnt, accum, dwqkv, dwo, dg, db, dg_post, what, s)
+                                       : lab_chunk<128, true>(a, f, cnt, accum, dwqkv, dwo, dg, db, dg_post, what, s))
+                            : (C == 64 ? lab_chunk<64, false>(a, f, cnt, accum, dwqkv, dwo, dg, db, nullptr, what, s)
+                                       : lab_chunk<128, false>(a, f, cnt, accum, dwqkv, dwo, dg, db, nullptr, what, s));
+        accum = 1;
+        return rc;
+    };
+    if (inner <= SG) {
+        const int per = SG / inner;
+        for (int o0 = 0; o0 < outer; o0 += per) {
+            const int no = outer - o0 < per ? outer - o0 : per;
+            if (const int rc = chunk((int64_t)o0 * so, inner, no * inner)) return rc;
+        }
+    } else {
+        for (int o = 0; o < outer; ++o)
+            for (int i0 = 0; i0 < inner; i0 += SG) {
+                const int cnt = inner - i0 < SG ? inner - i0 : SG;
+                if (const int rc = chunk((int64_t)o * so + (int64_t)i0 * si, cnt, cnt)) return rc;
+            }
+    }
+    return sdc::check_launch(what);
+}
 
-extern "C" size_t sdc_linattn_block_bwd_bytes(int outer, int inner, int C, int64_t n) {
+size_t lab_bytes(int outer, int inner, int C, int64_t n, bool post) {
     if (outer <= 0 || inner <= 0 || n <= 0 || n % TT != 0 || (C != 64 && C != 128)) return 0;
     const int64_t nseq = (int64_t)outer * inner;
     const int ns = pick_nsplit(nseq, (int)(n / TT));
     const int SG = lab_slots(ns);
-    return sizeof(float) * (size_t)lab_layout(C, ns, (int)(nseq < SG ? nseq : SG)).total;
+    return sizeof(float) * (size_t)lab_layout(C, ns, (int)(nseq < SG ? nseq : SG), post).total;
 }
+
+}  // namespace
+
+extern "C" size_t sdc_linattn_block_bwd_bytes(int outer, int inner, int C, int64_t n) { return lab_bytes(outer, inner, C, n, false); }
 
 extern "C" int sdc_linattn_block_bwd(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
                                      const float* dy, float* dx, float* dg, float* dwqkv, float* dwo, float* dbo, void* work,
@@ -631,51 +839,51 @@ extern "C" int sdc_linattn_block_bwd(const float* x, const float* g_pre, const f
     SDC_REQUIRE(C == 64 || C == 128, SDC_EINVAL, "sdc_linattn_block_bwd: dim must be 64 or 128 (got %d)", C);
     SDC_REQUIRE(outer > 0 && inner > 0 && n > 0 && n % TT == 0, SDC_EINVAL, "sdc_linattn_block_bwd: tokens must be a multiple of 64");
     SDC_REQUIRE(n / TT < (1ll << 24), SDC_EINVAL, "sdc_linattn_block_bwd: too many tokens");
-    const int64_t nseq = (int64_t)outer * inner;
-    SDC_REQUIRE(nseq < 65536, SDC_EINVAL, "sdc_linattn_block_bwd: outer*inner must be < 65536");
+    SDC_REQUIRE((int64_t)outer * inner < 65536, SDC_EINVAL, "sdc_linattn_block_bwd: outer*inner must be < 65536");
     SDC_REQUIRE(sc > 0 && sc < (1ll << 27), SDC_EINVAL,
                 "sdc_linattn_block_bwd: channel stride must stay below 2^27 elements (32-bit lane offsets)");
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wqkv) % 16 == 0 && reinterpret_cast<uintptr_t>(wo) % 16 == 0, SDC_EINVAL,
                 "sdc_linattn_block_bwd: wqkv / wo must be 16-byte aligned");
     SDC_REQUIRE(dx != x && dx != dy, SDC_EINVAL, "sdc_linattn_block_bwd: dx must not alias x or dy");
+    return lab_backward("sdc_linattn_block_bwd", x, g_pre, wqkv, wo, bo, nullptr, dy, dx, dg, dwqkv, dwo, dbo, nullptr, work, outer,
+                        inner, C, n, so, sc, si, 0, -1, eps, stream);
+}
 
-    LabArgs a;
-    a.x = x; a.dy = dy; a.g = g_pre; a.wqkv = wqkv; a.wo = wo; a.dx = dx; a.ws = static_cast<float*>(work);
-    a.ntiles = (int)(n / TT);
-    a.ns0 = pick_nsplit(nseq, a.ntiles);
-    a.tiles_per_split = (a.ntiles + a.ns0 - 1) / a.ns0;
-    a.nsplit = (a.ntiles + a.tiles_per_split - 1) / a.tiles_per_split;      // no empty splits (as the forward)
-    const int SG = lab_slots(a.ns0);
-    a.L = lab_layout(C, a.ns0, (int)(nseq < SG ? nseq : SG));
-    a.inner = inner; a.eps = eps; a.so = so; a.sc = sc; a.si = si;
-    LaArgs f{};
-    f.g_pre = g_pre; f.wqkv = wqkv; f.wo = wo; f.part = a.ws + a.L.part;
-    f.nsplit = a.nsplit; f.tiles_per_split = a.tiles_per_split; f.ntiles = a.ntiles; f.tiles_per_blk = 1;
-    f.pre_mode = 0; f.post_mode = -1; f.eps = eps; f.so = so; f.sc = sc; f.si = si;
-    hipStream_t s = sdc::as_stream(stream);
-    hipLaunchKernelGGL(lab_wt_kernel, dim3(C), dim3(NT), 0, s, wqkv, a.ws + a.L.wt, C);
-    // chunks of at most SG sequences: whole outer indices while they fit, else runs of one outer index's sequences
-    int accum = 0;
-    auto chunk = [&](int64_t off, int cinner, int cnt) -> int {
-        a.x = x + off; a.dy = dy + off; a.dx = dx + off; a.inner = cinner;
-        f.x = a.x; f.inner = cinner;
-        const int rc = C == 64 ? lab_chunk<64>(a, f, cnt, accum, dwqkv, dwo, dg, bo ? dbo : nullptr, s)
-                               : lab_chunk<128>(a, f, cnt, accum, dwqkv, dwo, dg, bo ? dbo : nullptr, s);
-        accum = 1;
-        return rc;
-    };
-    if (inner <= SG) {
-        const int per = SG / inner;
-        for (int o0 = 0; o0 < outer; o0 += per) {
-            const int no = outer - o0 < per ? outer - o0 : per;
-            if (const int rc = chunk((int64_t)o0 * so, inner, no * inner)) return rc;
-        }
-    } else {
-        for (int o = 0; o < outer; ++o)
-            for (int i0 = 0; i0 < inner; i0 += SG) {
-                const int cnt = inner - i0 < SG ? inner - i0 : SG;
-                if (const int rc = chunk((int64_t)o * so + (int64_t)i0 * si, cnt, cnt)) return rc;
-            }
-    }
-    return sdc::check_launch("sdc_linattn_block_bwd");
+extern "C" size_t sdc_linattn_block_post_bwd_bytes(int outer, int inner, int C, int64_t n) { return lab_bytes(outer, inner, C, n, true); }
+
+extern "C" int sdc_linattn_block_post_bwd(const float* x, const float* g_pre, const float* wqkv, const float* wo, const float* bo,
+                                          const float* g_post, const float* dy, float* dx, float* dg_pre, float* dwqkv, float* dwo,
+                                          float* dbo, float* dg_post, void* work, int outer, int inner, int C, int64_t n, int64_t so,
+                                          int64_t sc, int64_t si, int pre_mode, int post_mode, float eps, void* stream) {
+    SDC_REQUIRE(x, SDC_ENULL, "sdc_linattn_block_post_bwd: null x");
+    SDC_REQUIRE(g_pre, SDC_ENULL, "sdc_linattn_block_post_bwd: null g_pre");
+    SDC_REQUIRE(wqkv, SDC_ENULL, "sdc_linattn_block_post_bwd: null wqkv");
+    SDC_REQUIRE(wo, SDC_ENULL, "sdc_linattn_block_post_bwd: null wo");
+    SDC_REQUIRE(g_post, SDC_ENULL, "sdc_linattn_block_post_bwd: null g_post");
+    SDC_REQUIRE(dy, SDC_ENULL, "sdc_linattn_block_post_bwd: null dy");
+    SDC_REQUIRE(dx, SDC_ENULL, "sdc_linattn_block_post_bwd: null dx");
+    SDC_REQUIRE(dg_pre, SDC_ENULL, "sdc_linattn_block_post_bwd: null dg_pre");
+    SDC_REQUIRE(dwqkv, SDC_ENULL, "sdc_linattn_block_post_bwd: null dwqkv");
+    SDC_REQUIRE(dwo, SDC_ENULL, "sdc_linattn_block_post_bwd: null dwo");
+    SDC_REQUIRE(dg_post, SDC_ENULL, "sdc_linattn_block_post_bwd: null dg_post");
+    SDC_REQUIRE(work, SDC_ENULL, "sdc_linattn_block_post_bwd: null work");
+    SDC_REQUIRE(!bo || dbo, SDC_ENULL, "sdc_linattn_block_post_bwd: null dbo although bo is given");
+    SDC_REQUIRE(pre_mode == 0 || pre_mode == 1, SDC_EINVAL,
+                "sdc_linattn_block_post_bwd: pre norm mode %d is not supported (0 channel LayerNorm, 1 RMSNorm)", pre_mode);
+    SDC_REQUIRE(post_mode != -1, SDC_EINVAL,
+                "sdc_linattn_block_post_bwd: post norm mode -1 (no post norm) is sdc_linattn_block_bwd's form");
+    SDC_REQUIRE(post_mode == 0 || post_mode == 1, SDC_EINVAL,
+                "sdc_linattn_block_post_bwd: post norm mode %d is not supported (0 channel LayerNorm, 1 RMSNorm)", post_mode);
+    SDC_REQUIRE(C == 64 || C == 128, SDC_EINVAL, "sdc_linattn_block_post_bwd: dim must be 64 or 128 (got %d)", C);
+    SDC_REQUIRE(outer > 0 && inner > 0 && n > 0 && n % TT == 0, SDC_EINVAL, "sdc_linattn_block_post_bwd: tokens must be a multiple of 64");
+    SDC_REQUIRE(n / TT < (1ll << 24), SDC_EINVAL, "sdc_linattn_block_post_bwd: too many tokens");
+    SDC_REQUIRE((int64_t)outer * inner < 65536, SDC_EINVAL, "sdc_linattn_block_post_bwd: outer*inner must be < 65536");
+    SDC_REQUIRE(sc > 0 && sc < (1ll << 27), SDC_EINVAL,
+                "sdc_linattn_block_post_bwd: channel stride must stay below 2^27 elements (32-bit lane offsets)");
+    SDC_REQUIRE(reinterpret_cast<uintptr_t>(wqkv) % 16 == 0, SDC_EINVAL, "sdc_linattn_block_post_bwd: wqkv must be 16-byte aligned");
+    SDC_REQUIRE(reinterpret_cast<uintptr_t>(wo) % 16 == 0, SDC_EINVAL, "sdc_linattn_block_post_bwd: wo must be 16-byte aligned");
+    SDC_REQUIRE(dx != x, SDC_EINVAL, "sdc_linattn_block_post_bwd: dx must not alias x");
+    SDC_REQUIRE(dx != dy, SDC_EINVAL, "sdc_linattn_block_post_bwd: dx must not alias dy");
+    return lab_backward("sdc_linattn_block_post_bwd", x, g_pre, wqkv, wo, bo, g_post, dy, dx, dg_pre, dwqkv, dwo, dbo, dg_post, work,
+                        outer, inner, C, n, so, sc, si, pre_mode, post_mode, eps, stream);
 }

@@ -269,6 +269,47 @@ def linattn_block_bwd(x, g, wqkv_p, wo_p, bo, dy, eps=1e-5, work=None):
     return dx, dg, dwqkv, dwo, dbo
 
 
+def _linattn_post_geom(x):
+    B, Cc = x.shape[:2]
+    n = x.numel() // (B * Cc)
+    return B, 1, Cc, n, Cc * n, n, 0
+
+
+def linattn_post_block(x, g_pre, wqkv_p, wo_p, bo, g_post, mode_pre, mode_post, eps=1e-5):
+    """the fused post-norm LinearAttention block of the 1-D nets in literal fp32 (sdc_linattn_block_sel, impl 0): x (B, C, ...)
+    contiguous, every axis behind C a token axis, C in {64, 128}, tokens % 64 == 0; g_pre, g_post (C), wqkv_p packed [C][384], wo_p
+    packed [128][C], bo (C) or None; modes 0 (channel LayerNorm) / 1 (RMSNorm) -> y"""
+    _need_cuda(x, g_pre, wqkv_p, wo_p, bo, g_post)
+    lib = _lib.get_lib()
+    geom = _linattn_post_geom(x)
+    y = torch.empty_like(x)
+    work = torch.empty(int(lib.sdc_linattn_block_bytes(geom[0], geom[1], geom[2], geom[3])) // 4, dtype=torch.float32, device=x.device)
+    check(lib.sdc_linattn_block_sel(x.data_ptr(), g_pre.data_ptr(), wqkv_p.data_ptr(), wo_p.data_ptr(), 0 if bo is None else bo.data_ptr(),
+                                    g_post.data_ptr(), work.data_ptr(), y.data_ptr(), *geom, int(mode_pre), int(mode_post), eps, 0,
+                                    _stream(x)), "sdc_linattn_block_sel")
+    return y
+
+
+def linattn_post_block_bwd(x, g_pre, wqkv_p, wo_p, bo, g_post, dy, mode_pre, mode_post, eps=1e-5, work=None):
+    """backward of linattn_post_block from x and dy alone (sdc_linattn_block_post_bwd) -> (dx, dg_pre, dwqkv_p, dwo_p, dbo | None,
+    dg_post); the gradients of the weights come in the packed layouts of wqkv_p and wo_p"""
+    _need_cuda(x, g_pre, wqkv_p, wo_p, bo, g_post, dy)
+    lib = _lib.get_lib()
+    geom = _linattn_post_geom(x)
+    dx, dg, dwqkv, dwo = torch.empty_like(x), torch.empty_like(g_pre), torch.empty_like(wqkv_p), torch.empty_like(wo_p)
+    dgp = torch.empty_like(g_post)
+    dbo = None if bo is None else torch.empty_like(bo)
+    if work is None:
+        work = torch.empty(int(lib.sdc_linattn_block_post_bwd_bytes(geom[0], geom[1], geom[2], geom[3])) // 4, dtype=torch.float32,
+                           device=x.device)
+    check(lib.sdc_linattn_block_post_bwd(x.data_ptr(), g_pre.data_ptr(), wqkv_p.data_ptr(), wo_p.data_ptr(),
+                                         0 if bo is None else bo.data_ptr(), g_post.data_ptr(), dy.data_ptr(), dx.data_ptr(),
+                                         dg.data_ptr(), dwqkv.data_ptr(), dwo.data_ptr(), 0 if dbo is None else dbo.data_ptr(),
+                                         dgp.data_ptr(), work.data_ptr(), *geom, int(mode_pre), int(mode_post), eps, _stream(x)),
+          "sdc_linattn_block_post_bwd")
+    return dx, dg, dwqkv, dwo, dbo, dgp
+
+
 def linattn_core(qkv, out, heads, outer, inner, n, qs, os_):
     """linear attention core (sdc_linattn): strides (so, sc, si) of qkv and out"""
     lib = _lib.get_lib()

@@ -319,9 +319,12 @@ class _HipUNet(nn.Module):
         # today's chain (norm -> 1x1 -> core -> 1x1 -> add), bit for bit; True (opt-in) = the sites the sampler plans fuse (width 64 /
         # 128, H W % 64 == 0, B F < 65536, contiguous, fuse_linattn on) as ONE node: forward sdc_linattn_block_sel (impl 0, literal
         # fp32), backward sdc_linattn_block_bwd, which recomputes everything from x and dy -- only x is saved instead of x, xn, qkv and
-        # the core's output.  fp32 in another summation order; independent of train_fuse_attn and train_precision.  Wider sites, the
-        # 1-D nets (their LinearAttention has a post norm), net(x, t) and the samplers never see it; a live GraphedLossStep keeps the
-        # mode it was captured with.  Only booleans are accepted (ValueError otherwise).
+        # the core's output.  On the 1-D nets (Unet2D / Unet1D) the same switch covers Residual(PreNorm(LinearAttention)), whose
+        # to_out ends in a second channel norm: width 64 / 128, tokens % 64 == 0, B < 65536, contiguous, fuse_linattn on -> ONE node,
+        # forward sdc_linattn_block_sel (impl 0, both norms of the net's NORM_MODE), backward sdc_linattn_block_post_bwd; x is saved
+        # instead of x, xn, qkv, the core's output and the pre-norm z.  fp32 in another summation order; independent of
+        # train_fuse_attn and train_precision.  Wider sites, net(x, t) and the samplers never see it; a live GraphedLossStep keeps
+        # the mode it was captured with.  Only booleans are accepted (ValueError otherwise).
         self.train_fuse_linattn = False
         # 7-tap stem conv (init_conv) of the sampler plans -- model(x, t), graph-replayed or eager, and the samplers -- on the fp16
         # matrix pipe (opt-in): fp16 operands rounded to nearest even, fp32 accumulation, where conv_stem_f16_kernel covers it

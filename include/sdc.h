@@ -445,7 +445,12 @@ int sdc_conformal_score(const SdcStepDesc* d, const float* pred, const float* tr
  * burgers_numeric_solve_free, 1D/data/generate_burgers.py:207-299, called by control_trajectories,
  * 1D/utils/metrics.py:42-65.  u0 (N,s), f (N,Nt,s) -> traj (N,Nt+1,s); `steps` Euler steps of size dt, the force row
  * advances and a snapshot is recorded every `record_every` steps; coef_transport = 1/(2 dx), d0..d2 = visc*[1,-2,1]/dx^2
- * (all rounded to fp32 by the caller exactly as the reference's FloatTensor(...) does). */
+ * (all rounded to fp32 by the caller exactly as the reference's FloatTensor(...) does).
+ * Step counts the reference's loop fails on are defined here: when record_every does not divide `steps` into Nt intervals, the
+ * steps past Nt * record_every run with zero force and at most Nt snapshots are recorded (rows never recorded stay unwritten);
+ * record_every <= 0 (the reference's steps < Nt, a modulo by zero) is SDC_EINVAL.  s > 8190 (two (s+2)-float rows exceed 64 KiB
+ * of LDS) is SDC_EINVAL.  All checks come before any launch.  The Python drop-in solvers.burgers_numeric_solve_free does not
+ * rely on the guards: it raises the reference's IndexError / ZeroDivisionError for those step counts before calling this. */
 int sdc_burgers_rollout(const float* u0, const float* f, float* traj, int N, int s, int Nt, int steps, int record_every,
                         float dt, float coef_transport, float d0, float d1, float d2, void* stream);
 

@@ -4,14 +4,17 @@
 // 10 000 Euler steps of   u_i += dt * ( -1/2 * (u^2_{i+1} - u^2_{i-1}) / (2 dx) + visc * (u_{i-1} - 2 u_i + u_{i+1}) / dx^2 + f_i )
 // with zero Dirichlet ghosts, the force switching every steps/Nt steps.  The reference spends ~8 torch launches per
 // step; here one workgroup per trajectory keeps u in LDS (ping-pong, one barrier per step) for the whole rollout.
-// Arithmetic is written with explicit round-to-nearest mul/add (no FMA contraction) in the reference's operation
-// order, so results match the fp32 CPU run bit for bit.
+// Arithmetic is compiled with FMA contraction off, every product and sum rounded to nearest on its own in the reference's
+// operation order, fp32 denormals kept, so results match the fp32 CPU run bit for bit (tests/test_gpu_solver.py).
 #include "sdc_common.h"
 
 namespace {
 
 __global__ void burgers_rollout_kernel(const float* __restrict__ u0, const float* __restrict__ f, float* __restrict__ traj,
                                        int s, int Nt, int steps, int rec, float dt, float ct, float d0, float d1, float d2) {
+    // hipcc contracts a * b + c into one FMA by default, and HIP's __fmul_rn / __fadd_rn are plain * and + that it contracts
+    // just the same: only this pragma, over operators written in this body, keeps every product and sum rounded on its own.
+#pragma clang fp contract(off)
     extern __shared__ float sh[];
     float* buf0 = sh;
     float* buf1 = sh + (s + 2);
@@ -37,10 +40,10 @@ __global__ void burgers_rollout_kernel(const float* __restrict__ u0, const float
             const float um = cur[i], uc = cur[i + 1], up = cur[i + 2];
             const float fv = fidx < Nt ? fn[(int64_t)fidx * s + i] : 0.f;
             // einsum('nsi,si->ns'): products summed in index order
-            const float tr = __fadd_rn(__fmul_rn(__fmul_rn(um, um), nct), __fmul_rn(__fmul_rn(up, up), ct));
-            const float df = __fadd_rn(__fadd_rn(__fmul_rn(um, d0), __fmul_rn(uc, d1)), __fmul_rn(up, d2));
-            const float rhs = __fadd_rn(__fadd_rn(__fmul_rn(-0.5f, tr), df), fv);
-            const float un = __fadd_rn(uc, __fmul_rn(dt, rhs));
+            const float tr = (um * um) * nct + (up * up) * ct;
+            const float df = (um * d0 + uc * d1) + up * d2;
+            const float rhs = (-0.5f * tr + df) + fv;
+            const float un = uc + dt * rhs;
             nxt[i + 1] = un;
             if (record) tn[(int64_t)(c + 1) * s + i] = un;
         }

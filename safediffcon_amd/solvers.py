@@ -13,7 +13,9 @@ from ._lib import check
 
 
 def burgers_numeric_solve_free(u0, f, visc, T, dt=1e-4, num_t=10, mode=None):
-    """u0 (N,s), f (N,Nt,s) on the HIP device -> trajectory (N, Nt+1, s).  Same signature / semantics as the reference."""
+    """u0 (N,s), f (N,Nt,s) on the HIP device -> trajectory (N, Nt+1, s).  Same signature / semantics as the reference,
+    its exceptions included: ValueError for mode="const", AssertionError for num_t, IndexError when Nt does not divide the step
+    count, ZeroDivisionError for fewer steps than intervals."""
     if mode == "const":
         raise ValueError
     assert f.size(1) == num_t, "check number of time interval"
@@ -25,6 +27,11 @@ def burgers_numeric_solve_free(u0, f, visc, T, dt=1e-4, num_t=10, mode=None):
     delta_x = 1.0 / (s + 1)
     steps = math.ceil(T / dt)
     record_time = math.floor(steps / Nt)
+    # the reference's loop fails on these two step counts; fail the same way, before any launch (the C entry has guards instead)
+    if 0 < steps < Nt:
+        raise ZeroDivisionError("integer modulo by zero")                    # j % record_time, record_time = 0
+    if steps > 0 and steps % Nt != 0:
+        raise IndexError(f"index {Nt} is out of bounds for dimension 1 with size {Nt}")   # f[:, f_idx, :] at step Nt * record_time
     # coefficients rounded to fp32 from float64 like torch.FloatTensor(np.stack(D.data) / (2*delta_x)) does
     ct = float(np.float32(1.0 / (2 * delta_x)))
     d = (visc * np.array([1.0, -2.0, 1.0]) / delta_x ** 2).astype(np.float32)

@@ -925,6 +925,30 @@ size_t sdc_kstar_lstm_floats(void);
 int sdc_kstar_rollout(const SdcKstarModel* m, const float* actions, int64_t act_b_stride, int64_t act_t_stride,
                       int64_t act_c_stride, double* out, double* work, int B, int nsteps, void* stream);
 
+/* ---- Closed loop: the reference's trained real-time controller inside the rollout (KSTARDataGenerator.auto_control /
+ * random_target_simulation, tokamak/kstar_data_generator_random_target.py:379-409,433-517; the actor is SB2_model.predict,
+ * tokamak/common/model_structure.py:191-204, bavg = 0).  The action of step t depends on rows t-1 .. t-3, so the controller
+ * runs in the kernel: per step it forms the observation (the last three (raw action, beta_p, q95, l_i) rows, oldest first,
+ * then the target of the step), evaluates the actor in fp64 (normalise 2(obs - low)/(high - low) - 1, relu layers, tanh head,
+ * 0.5 (high_a - low_a)(y + 1) + low_a; one thread per output column, k ascending) and hands the RAW output to the control /
+ * predict_0d code of sdc_kstar_rollout -- the same device code, a compile-time variant of one kernel, with the same three
+ * launch shapes; replaying a loop's quantised actuator values through sdc_kstar_rollout gives its rows bit for bit.
+ * Like the rollout, parity with the TensorFlow surrogate is unpinned. */
+typedef struct {
+    int nlayers;            /* hidden relu layers, <= 4 */
+    int width[6];           /* width[0] = 39 observation entries ... width[nlayers + 1] = 9 actuators, each <= 256 */
+    const float* params;    /* device memory; per layer: kernel[in][out], bias[out]; the tanh head last */
+    double low_state[39], high_state[39];   /* (LOW_ACTION + LOW_TARGET) * 3 + LOW_TARGET and its HIGH twin */
+    double hist0[12];       /* the row every history slot starts with: LOW_ACTION + TARGET_INIT */
+} SdcKstarPolicy;
+/* targets (B, nsteps, 3) fp64 [beta_p, q95, l_i], finite (the caller checks: the reference's int(nan) raises).
+ * rows (B, nsteps + 1, 8) as sdc_kstar_rollout's out (row 0: the steady-state network's); actions (B, nsteps, 9) the raw
+ * policy outputs before the clip; inputs (B, nsteps + 1, 15) the quantised simulator inputs after each control(), row 0 =
+ * inputs0; work: 4 doubles.  A policy with width[0] != 39, an output width other than 9, more than 4 hidden layers or a
+ * width outside 1..256 returns SDC_EINVAL and launches nothing. */
+int sdc_kstar_closed_loop(const SdcKstarModel* m, const SdcKstarPolicy* p, const double* targets, double* rows, double* actions,
+                          double* inputs, double* work, int B, int nsteps, void* stream);
+
 /* ---- Smoke score check: the fluid rollout behind InferencePipeline.multi_evaluate (2d/inference_2d.py:389-447 ->
  * 2d/dataset/apps/evaluate_solver.py:209-350 `solver`: per step get_envolve :82-111 = control ring + last interior velocity ->
  * divergence_free (phi/flow.py:317-326: float64 CG of phi/solver/base.py:63-103 on the matrix of phi/solver/sparse.py:27-77)

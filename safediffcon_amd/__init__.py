@@ -7,6 +7,8 @@ Drop-in classes (same names / signatures as the reference):
   ConformalCalculator, conformal helpers                  (safediffcon_amd.conformal)
   control_trajectories (Burgers rollout)                  (safediffcon_amd.solvers)
   KSTARSolver, control_trajectories, evaluate_samples     (safediffcon_amd.kstar: the tokamak score check)
+  KSTARDataGenerator, load_rl_policy, random_targets,
+  save_record                                             (safediffcon_amd.kstar: closed-loop rollouts under the RL controller)
   GraphedLossStep                                         (safediffcon_amd.train_graph: a fine-tuning step as one hipGraph)
   FusedOptimizer                                          (safediffcon_amd.optim: grad clip + SGD / Adam / AdamW + EMA, three launches)
 
@@ -19,5 +21,6 @@ from .diffusion import (GaussianDiffusion, GaussianDiffusionBurgers, GaussianDif
                         schedule_tables)
 from .train_graph import GraphedLossStep                                               # noqa: F401
 from .optim import FusedOptimizer                                                      # noqa: F401
+from .kstar import KSTARDataGenerator, load_rl_policy, random_targets, save_record     # noqa: F401
 
 __version__ = "0.1.0"

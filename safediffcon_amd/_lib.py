@@ -67,6 +67,11 @@ class SdcKstarModel(C.Structure):
                 ("low_action", C.c_double * 9), ("high_action", C.c_double * 9), ("year_in", C.c_double)]
 
 
+class SdcKstarPolicy(C.Structure):
+    _fields_ = [("nlayers", C.c_int32), ("width", C.c_int32 * 6), ("params", C.c_void_p), ("low_state", C.c_double * 39),
+                ("high_state", C.c_double * 39), ("hist0", C.c_double * 12)]
+
+
 # name -> (restype, argtypes); every symbol include/sdc.h declares
 SIGNATURES = {
     "sdc_version": (C.c_int, []),
@@ -189,6 +194,8 @@ SIGNATURES = {
     "sdc_sumpool2": (C.c_int, [_f32p, _f32p, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _stream]),
     "sdc_kstar_lstm_floats": (C.c_size_t, []),
     "sdc_kstar_rollout": (C.c_int, [C.POINTER(SdcKstarModel), _f32p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _stream]),
+    "sdc_kstar_closed_loop": (C.c_int, [C.POINTER(SdcKstarModel), C.POINTER(SdcKstarPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_int, _stream]),
     "sdc_smoke_rollout_workspace_bytes": (C.c_size_t, [C.c_int]),
     "sdc_smoke_rollout": (C.c_int, [_f32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _i64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,

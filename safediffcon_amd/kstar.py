@@ -10,6 +10,13 @@ sample at a time, 122 ``model.predict`` calls each; here the networks' weights a
 (``h5lite``; no TensorFlow, no h5py) and ``sdc_kstar_rollout`` carries the whole batch through the 122 rows in one launch.
 There is no CPU path: without ``libsdc_hip.so`` and a GPU every entry point raises.
 
+Closed loop, the reference's tokamak data generator:
+  KSTARDataGenerator().random_target_simulation(seed)   tokamak/kstar_data_generator_random_target.py:123-164, 379-531
+  SB2_model (the RL controller's actor)                 tokamak/common/model_structure.py:178-204
+``sdc_kstar_closed_loop`` runs the controller inside the rollout kernel (the action of step t needs rows t-1 .. t-3), one launch
+for a batch of seeds where tokamak/data_parallel_generate.py starts one TensorFlow process per seed; ``random_targets`` (host)
+restates the target schedule, ``load_rl_policy`` reads the controller's zip with zipfile + numpy.
+
 Keras semantics restated here (load order and layer maths) are spelled out in ``load_weights`` and ``csrc/sdc_kstar.hip``;
 the reference cannot be run in this image (TensorFlow absent), so this row's parity is *unpinned* -- see DESIGN.md section 9.
 """
@@ -252,6 +259,7 @@ class KSTARModel:
         d.year_in = YEAR_IN
         self.desc = d
         self._work = torch.empty(4, dtype=torch.float64, device=self.device)
+        self._policies = {}
 
     def rollout(self, actions, n_steps=N_STEPS):
         """actions: float32 CUDA tensor viewed as (B, >= n_steps, 9) -- any strides, e.g. ``diffused[:, 3:, :nt-1].permute(0, 2, 1)``
@@ -270,6 +278,178 @@ class KSTARModel:
                                          out.data_ptr(), self._work.data_ptr(), B, n_steps,
                                          torch.cuda.current_stream(actions.device).cuda_stream), "sdc_kstar_rollout")
         return out
+
+    def _device_policy(self, policy):
+        """the actor's parameters on this model's device + the descriptor sdc_kstar_closed_loop takes; cached per policy object"""
+        hit = self._policies.get(id(policy))
+        if hit is not None and hit[0] is policy:
+            return hit[1]
+        pol = load_rl_policy(policy)
+        names = [f"fc{i}" for i in range(len(pol["layers"]))] + ["dense"]
+        flat = np.concatenate([np.concatenate([pol[f"{n}_kernel"].reshape(-1), pol[f"{n}_bias"]]) for n in names]).astype(np.float32)
+        buf = torch.from_numpy(flat).to(self.device)
+        d = _lib.SdcKstarPolicy()
+        d.nlayers = len(names) - 1
+        d.width[0] = pol[f"{names[0]}_kernel"].shape[0]
+        for i, n in enumerate(names):
+            d.width[i + 1] = pol[f"{n}_kernel"].shape[1]
+        d.params = buf.data_ptr()
+        for i, (lo, hi) in enumerate(zip((LOW_ACTION + LOW_TARGET) * LOOKBACK + LOW_TARGET, (HIGH_ACTION + HIGH_TARGET) * LOOKBACK + HIGH_TARGET)):
+            d.low_state[i], d.high_state[i] = lo, hi
+        for i, v in enumerate(LOW_ACTION + TARGET_INIT):
+            d.hist0[i] = v
+        self._policies[id(policy)] = (policy, (d, buf))
+        return d, buf
+
+    def closed_loop(self, targets, policy, n_steps=N_STEPS):
+        """the reference's controller closed around the simulator (KSTARDataGenerator.auto_control + predict_0d per step,
+        kstar_data_generator_random_target.py:379-409,459-511), one launch for the batch.
+        targets: float64 / float32 tensor or array (B, n_steps, 3) of (βp, q95, li) per control step;  policy: what
+        ``load_rl_policy`` takes or returns.
+        -> (rows (B, n_steps + 1, 8), actions (B, n_steps, 9) raw policy outputs, inputs (B, n_steps + 1, 15) quantised
+        simulator inputs), float64 CUDA tensors; row 0 is the steady-state row, inputs[:, 0] the initial inputs"""
+        t = targets if isinstance(targets, torch.Tensor) else torch.from_numpy(np.array(targets))      # a copy: the array may be read-only
+        if t.dtype not in (torch.float64, torch.float32):
+            raise TypeError("targets must be float64 or float32")
+        if t.dim() != 3 or t.shape[1] != n_steps or t.shape[2] != 3 or n_steps < 1:
+            raise IndexError(f"targets must be (B, {n_steps}, 3), got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("cannot convert float NaN to integer")                                  # int() in f2i of the record / the control
+        if self.device.type != "cuda":
+            raise RuntimeError("safediffcon_amd.kstar runs on a GPU (libsdc_hip.so); there is no CPU path")
+        d, _ = self._device_policy(policy)
+        t = t.to(device=self.device, dtype=torch.float64).contiguous()
+        B = t.shape[0]
+        rows = torch.empty((B, n_steps + 1, 8), dtype=torch.float64, device=self.device)
+        actions = torch.empty((B, n_steps, 9), dtype=torch.float64, device=self.device)
+        inputs = torch.empty((B, n_steps + 1, 15), dtype=torch.float64, device=self.device)
+        if B == 0:
+            return rows, actions, inputs
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            check(self.lib.sdc_kstar_closed_loop(C.byref(self.desc), C.byref(d), t.data_ptr(), rows.data_ptr(), actions.data_ptr(),
+                                                 inputs.data_ptr(), self._work.data_ptr(), B, n_steps, stream), "sdc_kstar_closed_loop")
+        return rows, actions, inputs
+
+
+# ------------------------------------------------------------------------------------------------ the RL controller
+# constants of tokamak/kstar_data_generator_random_target.py:69-75,101-105
+LOW_TARGET, HIGH_TARGET = [0.8, 4.0, 0.80], [2.1, 7.0, 1.05]
+TARGET_INIT = [1.45, 5.5, 0.925]
+RAND_TARGET_MINS, RAND_TARGET_MAXS = [1.06, 4.6, 0.85], [1.84, 6.4, 1.00]
+LOOKBACK = 3
+N_OBS = (9 + 3) * LOOKBACK + 3
+RL_POLICY_ZIP = os.path.join("rl", "rt_control", "3frame_v220505", "best_model.zip")      # under the weights directory, :58-65
+
+
+def _check_policy(pol):
+    """shape rules of the device entry point, as ValueError"""
+    n = len(pol["layers"])
+    if n > 4:
+        raise ValueError(f"the policy has {n} hidden layers, at most 4 are supported")
+    width = N_OBS
+    for name in [f"fc{i}" for i in range(n)] + ["dense"]:
+        k, b = pol.get(f"{name}_kernel"), pol.get(f"{name}_bias")
+        if k is None or b is None:
+            raise ValueError(f"the policy lacks {name}_kernel / {name}_bias")
+        if k.ndim != 2 or b.shape != (k.shape[1],):
+            raise ValueError(f"the policy's {name} layer has kernel {k.shape} and bias {b.shape}")
+        if k.shape[0] != width:
+            raise ValueError(f"the policy's {name} layer takes {k.shape[0]} inputs, {width} arrive (the observation has {N_OBS} entries)")
+        width = k.shape[1]
+        if not 1 <= width <= 256:
+            raise ValueError(f"the policy's {name} layer is {width} wide, at most 256 are supported")
+    if width != 9:
+        raise ValueError(f"the policy drives {width} actuators, the simulator has 9")
+    return pol
+
+
+def load_rl_policy(src):
+    """the actor of the reference's controller as {"fc{i}_kernel", "fc{i}_bias", "dense_kernel", "dense_bias", "layers"}
+    (float32 arrays as stored).  ``src``: the stable-baselines zip the reference reads with numpy (SB2_model.__init__,
+    common/model_structure.py:179-184: members ``data`` (json, policy_kwargs["layers"], default [64, 64]) and ``parameters`` (an
+    npz holding model/pi/fc{i}/kernel:0, ...)), or a dict / .npz in that layout (tests/golden/kstar_rl_policy.npz)"""
+    if isinstance(src, dict):
+        raw = src
+    else:
+        import io
+        import zipfile
+        with zipfile.ZipFile(src) as zf:
+            members = set(zf.namelist())
+            if {"data", "parameters"} <= members:
+                layers = json.loads(zf.read("data").decode("utf-8")).get("policy_kwargs", {}).get("layers", [64, 64])
+                params = np.load(io.BytesIO(zf.read("parameters")))
+                raw = {k[len("model/pi/"):].replace(":0", "").replace("/", "_"): params[k] for k in params.files if k.startswith("model/pi/")}
+                raw["layers"] = np.array(layers)
+            else:
+                raw = None
+        if raw is None:
+            with np.load(src) as z:
+                raw = {k: z[k] for k in z.files}
+    if "layers" not in raw:
+        raise ValueError("the policy lacks 'layers' (the hidden widths)")
+    pol = {"layers": np.asarray(raw["layers"]).astype(np.int64).reshape(-1)}
+    for name in [f"fc{i}" for i in range(len(pol["layers"]))] + ["dense"]:
+        for part in ("kernel", "bias"):
+            if f"{name}_{part}" in raw:
+                pol[f"{name}_{part}"] = np.ascontiguousarray(raw[f"{name}_{part}"], dtype=np.float32)
+    return _check_policy(pol)
+
+
+def random_targets(seeds, n_steps=N_STEPS):
+    """the target sequences ``random_target_simulation(random_seed=seed)`` follows (:433-517), one per seed -> float64
+    (len(seeds), n_steps, 3) of (βp, q95, li).  ``np.random.seed(seed)`` there is ``RandomState(seed)`` here (the same stream,
+    the global state untouched); a target is three uniforms in the order βp, q95, li, each i2f(f2i(.)); the first holds for
+    the warm-up step and the three seconds after it (31 control steps), each later one for 30; the draw after the last step is
+    made like the reference's and unused."""
+    scale = _scale()
+    seeds = list(seeds)
+    out = np.empty((len(seeds), n_steps, 3))
+
+    def draw(rs):
+        return [float(int(rs.uniform(lo, hi) * scale) / scale) for lo, hi in zip(RAND_TARGET_MINS, RAND_TARGET_MAXS)]
+
+    for n, seed in enumerate(seeds):
+        rs = np.random.RandomState(seed)
+        target = draw(rs)
+        for step in range(n_steps):
+            out[n, step] = target
+            if step > 0 and step % 30 == 0:
+                target = draw(rs)
+    return out
+
+
+def save_record(path, record):
+    """the reference's file layout (:521-531): ``np.load(path, allow_pickle=True)["data"].item()`` gives the record back"""
+    np.savez_compressed(path, data=np.array(record))
+
+
+class KSTARDataGenerator:
+    """``KSTARDataGenerator().random_target_simulation(random_seed)`` of tokamak/kstar_data_generator_random_target.py, and the
+    batch form ``generate(seeds)`` that replaces data_parallel_generate.py's one process per seed with one launch.
+    ``weights``: as ``get_model``; ``policy``: as ``load_rl_policy``, None for the zip under the weights directory."""
+
+    def __init__(self, weights=None, policy=None, device="cuda", n_model_box=1):
+        if torch.device(device).type != "cuda":
+            raise RuntimeError("safediffcon_amd.kstar runs on a GPU (libsdc_hip.so); there is no CPU path")
+        if policy is None:
+            if weights is not None and not isinstance(weights, (str, os.PathLike)):
+                raise ValueError("policy=None looks for the controller under a weights directory; pass the policy itself")
+            policy = os.path.join(default_weights_dir() if weights is None else weights, RL_POLICY_ZIP)
+        self.policy = load_rl_policy(policy)
+        self.model = get_model(weights, device, n_model_box)
+
+    def generate(self, seeds):
+        """-> one record per seed: {"inputs": (122, 15), "outputs": (122, 8), "targets": (122, 3), "actions": (121, 9)} float64
+        arrays in the reference's row conventions (row 0 the steady state; the first target twice, :452-472)"""
+        targets = random_targets(seeds)
+        rows, actions, inputs = (x.cpu().numpy() for x in self.model.closed_loop(targets, self.policy))
+        return [{"inputs": inputs[n], "outputs": rows[n], "targets": np.concatenate([targets[n, :1], targets[n]]), "actions": actions[n]}
+                for n in range(len(targets))]
+
+    def random_target_simulation(self, random_seed=0):
+        """one trajectory; the reference writes it to data/<seed>.npz, here ``save_record`` does that on request"""
+        return self.generate([random_seed])[0]
 
 
 def default_weights_dir():

@@ -973,6 +973,36 @@ int sdc_smoke_rollout(const float* c1, const float* c2, int64_t ctrl_b_stride, i
                       int n_buckets, int n_safe, double* out, double* out_zero, void* work, size_t work_bytes, int B, int nt,
                       int nx, int per_timelength, int ring_lo, int ring_hi, double accuracy, int max_iterations, void* stream);
 
+/* Smoke data generator (2d/dataset/apps/a_gen_dataset_128.py `loop_write`): the same fluid step as sdc_smoke_rollout, one
+ * workgroup per trajectory, with the loop closed inside the kernel -- on frame f = 1 .. T the velocity outside [16:112, 16:112]
+ * is the previous frame's projected velocity plus the ring field of the frame (or, on the frames the schedule marks absolute,
+ * the ring field itself); interior cells keep the previous velocity.  Where the ring numbers come from is the caller's business.
+ *   ring            (B, T, 128, 128, 2) fp64, batch / frame strides in elements (both even), a frame dense; only cells outside
+ *                   [16:112, 16:112] are read; 16-byte aligned
+ *   start_yx        (B, 2) int32: the 10 x 10 square of ones on the 127 x 127 density grid starts at (y0, x0)
+ *   schedule        (B, T) bytes, entry f - 1 for frame f: bit 0 = 1 the ring field is the value / 0 it is added to the previous
+ *                   velocity; bits 1-2 = 0 no book-keeping, 1 book-keeping then record, 2 record then book-keeping (a frame is
+ *                   recorded when f % rs == 0, whatever these bits say, so every output element is written)
+ *   map_index       (B) int32 into label_maps (n_maps, 128, 128) bytes: 0 = none, k = absorbing area k - 1, areas must not
+ *                   overlap; map_buckets = HOST array of n_maps bucket counts, each in [2, 8]; n_maps in [1, 4]
+ *   fluid_mask      (127, 127) bytes as for sdc_smoke_rollout; initial_vy: the initial velocity is (0, initial_vy) everywhere
+ *   outputs, fp64, n = T / rs + 1 recorded frames (frame 0 = the initial state), L = 128 / ss cells sub-sampled [::ss]:
+ *     density (B, n, L, L) (ss = 1: the 127 x 127 field inside a zero 128 x 128 frame), density_zero the same for the copy the
+ *     book-keeping empties (may be null), velocity and control (B, n, L, L, 2) (16-byte aligned; a control frame is the ring
+ *     value before the velocity mask, zero inside, of frame f = rec * rs + 1; the last one stays zero as in the reference),
+ *     smoke (B, n, smoke_cols): the cumulative amounts of the sample's nb areas, the emptied field's sum at column nb, zeros
+ *     after it; smoke_cols in [max bucket count + 1, 16]
+ *   work            sdc_smoke_datagen_workspace_bytes(B) bytes, 16-byte aligned
+ * T a multiple of rs, ss divides 128; accuracy / max_iterations as for sdc_smoke_rollout.  SDC_ENULL / SDC_EINVAL / SDC_EALIGN
+ * before any launch.  A sample's result depends on neither its batch nor its block index. */
+size_t sdc_smoke_datagen_workspace_bytes(int B);
+int sdc_smoke_datagen(const double* ring, int64_t ring_b_stride, int64_t ring_f_stride, const int32_t* start_yx,
+                      const unsigned char* schedule, const int32_t* map_index, const unsigned char* label_maps,
+                      const int32_t* map_buckets, int n_maps, const unsigned char* fluid_mask, double initial_vy,
+                      double* density, double* density_zero, double* velocity, double* control, double* smoke, int smoke_cols,
+                      void* work, size_t work_bytes, int B, int T, int rs, int ss, double accuracy, int max_iterations,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,10 @@ SIGNATURES = {
     "sdc_smoke_rollout": (C.c_int, [_f32p, _f32p, _i64, _i64, _f32p, _i64, _f32p, _i64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _stream]),
+    "sdc_smoke_datagen_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "sdc_smoke_datagen": (C.c_int, [C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int,
+                                    C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _stream]),
     "sdc_conv_splitk_bytes": (C.c_size_t, [C.POINTER(SdcConvDesc)]),
     "sdc_conv_splitk": (C.c_int, [C.POINTER(SdcConvDesc), _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_size_t, _stream]),
     "sdc_linear": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _i64, _i64, _stream]),

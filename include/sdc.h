@@ -1003,6 +1003,35 @@ int sdc_smoke_datagen(const double* ring, int64_t ring_b_stride, int64_t ring_f_
                       void* work, size_t work_bytes, int B, int T, int rs, int ss, double accuracy, int max_iterations,
                       void* stream);
 
+/* --------------------------------------------------- Burgers data generator */
+/* What 1D/data/generate_burgers.py does to make the 1-D Burgers task's training data (csrc/sdc_burgers_gen.hip).
+ *
+ * sdc_burgers_rollout_wave: the Euler rollout of sdc_burgers_rollout -- the same expressions in the same order, FMA contraction
+ * off, fp32 denormals kept, so the same bits -- with one wave per trajectory and the state in registers: lane l owns the
+ * K = ceil(s / 64) cells [l K, l K + K), K in {1, 2, 4, 8}, so s <= 512 (more is SDC_EINVAL); no LDS, no barrier.  Cells >= s and the
+ * two neighbours outside the wave are the Dirichlet ghosts, +0.0f on every step.
+ *   u0 (Nu0, s) contiguous; force value of trajectory n, interval t, cell c: f[fi * f_sn + t * f_st + c] (element strides >= 0;
+ *   f_st = 0: one force row for every interval, the reference's mode='const'); traj (N, Nt + 1, s) contiguous, row 0 = u0.
+ *   pair_mode 0: ui = fi = n, needs Nu0 == Nf == N (burgers_numeric_solve_free);
+ *   pair_mode 1: ui = n / Nf, fi = n % Nf, needs N == Nu0 * Nf (burgers_numeric_solve: every u0 against every f).
+ *   Nt intervals of `rec` steps each (rec <= 0 is SDC_EINVAL); dt, coef_transport, d0..d2 as for sdc_burgers_rollout.
+ *   waves_per_block: 0 = the library's choice (4), else 1 .. 16; waves share nothing, so it changes no result.
+ * SDC_ENULL / SDC_EINVAL before any launch, the output untouched. */
+int sdc_burgers_rollout_wave(const float* u0, const float* f, float* traj, int N, int Nu0, int Nf, int s, int Nt, int rec,
+                             int64_t f_sn, int64_t f_st, int pair_mode, float dt, float coef_transport, float d0, float d1, float d2,
+                             int waves_per_block, void* stream);
+
+/* sdc_burgers_synth: the initial states and forces of make_data_varying_f / make_data (generate_burgers.py:302-418) from their drawn
+ * parameters, evaluated in float64 in the reference's operation order (contraction off) and rounded once to fp32.
+ *   upar (Nu0, 6) fp64 {loc1, amp1, sig1, loc2, amp2, sig2}; fpar (Nf, 8, 5) fp64 {amp, xloc, xsig, tloc, tsig} per term (amp with
+ *   its randint factor, the sigmas with their 0.5, multiplied on the host); x (s), ts (Nt) the fp32 grids; mask (s) fp32 or null.
+ *   e(d, sig) = exp((-0.5 (d d)) / (sig sig));  u0 = amp1 e(x - loc1, sig1) + amp2 e(x - loc2, sig2);
+ *   term_k = (amp_k (e(x - xloc_k, xsig_k) [mask])) (comp e(ts - tloc_k, tsig_k)), f = ((term_0 + term_1) + ...) + term_7 -> fp32,
+ *   then, if alpha != 1, min(max(f alpha, -10), 10) in fp32.  ts == null: make_data's form, term_k = amp_k e(...), Nt must be 1.
+ *   u0 (Nu0, s) fp32 and f (Nf, Nt, s) fp32; either may be null (skipped, with its parameters), not both. */
+int sdc_burgers_synth(const double* upar, const double* fpar, const float* x, const float* ts, const float* mask, double comp,
+                      float alpha, float* u0, float* f, int Nu0, int Nf, int s, int Nt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

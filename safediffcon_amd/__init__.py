@@ -10,6 +10,7 @@ Drop-in classes (same names / signatures as the reference):
   KSTARDataGenerator, load_rl_policy, random_targets,
   save_record                                             (safediffcon_amd.kstar: closed-loop rollouts under the RL controller)
   SmokeDataGenerator, random_scenes                       (safediffcon_amd.smoke_datagen: the smoke task's training-data generator)
+  BurgersDataGenerator, burgers_numeric_solve             (safediffcon_amd.burgers_datagen: the Burgers task's training-data generator)
   GraphedLossStep                                         (safediffcon_amd.train_graph: a fine-tuning step as one hipGraph)
   FusedOptimizer                                          (safediffcon_amd.optim: grad clip + SGD / Adam / AdamW + EMA, three launches)
 
@@ -24,5 +25,6 @@ from .train_graph import GraphedLossStep                                        
 from .optim import FusedOptimizer                                                      # noqa: F401
 from .kstar import KSTARDataGenerator, load_rl_policy, random_targets, save_record     # noqa: F401
 from .smoke_datagen import SmokeDataGenerator, random_scenes                           # noqa: F401
+from .burgers_datagen import BurgersDataGenerator, burgers_numeric_solve              # noqa: F401
 
 __version__ = "0.1.0"

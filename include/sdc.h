@@ -360,7 +360,13 @@ int sdc_tattn_block_x3_impl(int C, int ntok, int inner);
 /* Attention core (heads x 32): out = softmax(q*scale . k^T + bias) v, optional rotary on q,k.
  * 1D/model/unet.py:247-251 ; conv3d.py:313-353 (focus_present_mask all-False).
  * Sequences are indexed (outer, inner); element (o, c, i, tok) at o*so + c*sc + i*si + tok*st.
- * rot: [ntok][16][2] cos/sin table or null; bias: [heads][ntok][ntok] or null. ntok <= 256. */
+ * rot: [ntok][16][2] cos/sin table or null; bias: [heads][ntok][ntok] or null.
+ * Two domains.  ntok <= 256: everything above, any strides.  256 < ntok <= 4096: the streaming kernel
+ * (csrc/sdc_attn_long.hip) -- rot and bias null, tokens contiguous in qkv and out (q_st == o_st == 1).  Its address
+ * arithmetic is 64-bit; the 32-bit quantities are the token index and the grid outer*inner*heads*ceil(ntok/128) (checked
+ * per call), so the cap is not an arithmetic limit: 4096 is the largest size held against the fp64 reference.  Anything
+ * else past 256 tokens is SDC_EINVAL before any launch.  The kernel is chosen by ntok and the strides alone, never by
+ * outer or inner. */
 int sdc_attn(const float* qkv, float* out, const float* rot, const float* bias, int outer, int inner, int heads,
              int ntok, int64_t q_so, int64_t q_sc, int64_t q_si, int64_t q_st,
              int64_t o_so, int64_t o_sc, int64_t o_si, int64_t o_st, void* stream);
@@ -711,7 +717,9 @@ int sdc_pack_batch_run(const SdcPackItem* items_dev, int n, int total_blocks, in
 /* Backward of the attention cores (same tensor conventions as sdc_attn / sdc_linattn: q, k, v = channel ranges of qkv, the
  * gradients dqkv in the same layout; dout = dL/dout in the layout of `out`).
  * sdc_attn_bwd: dbias (heads, ntok, ntok) = sum over sequences of dS, or null (built for ntok <= 32: the temporal attention's
- * relative-position bias, conv3d.py:74-112); work = sdc_attn_bwd_bytes(...) bytes when dbias is requested. */
+ * relative-position bias, conv3d.py:74-112); work = sdc_attn_bwd_bytes(...) bytes when dbias is requested.
+ * 256 < ntok <= 4096 (the domain of sdc_attn above, dbias null): work is REQUIRED -- two floats per (sequence, head, token),
+ * the row statistics the gradient recomputes the probabilities from; nothing ntok x ntok is stored, no atomics. */
 size_t sdc_attn_bwd_bytes(int outer, int inner, int heads, int ntok);
 int sdc_attn_bwd(const float* qkv, const float* dout, const float* rot, const float* bias, float* dqkv, float* dbias, void* work,
                  int outer, int inner, int heads, int ntok, int64_t q_so, int64_t q_sc, int64_t q_si, int64_t q_st,

@@ -4,6 +4,7 @@
 // Both read q,k,v straight out of the channel-major conv output through strides, so no permute /
 // rearrange copy is ever materialised ('b (h c) x y -> b h c (x y)', 'b c f h w -> b (h w) f c').
 #include "sdc_common.h"
+#include "sdc_attn_long.h"
 
 namespace {
 
@@ -572,8 +573,11 @@ extern "C" int sdc_attn(const float* qkv, float* out, const float* rot, const fl
                         int heads, int ntok, int64_t q_so, int64_t q_sc, int64_t q_si, int64_t q_st, int64_t o_so,
                         int64_t o_sc, int64_t o_si, int64_t o_st, void* stream) {
     SDC_REQUIRE(qkv && out, SDC_ENULL, "sdc_attn: null pointer");
-    SDC_REQUIRE(outer > 0 && inner > 0 && heads > 0 && ntok > 0 && ntok <= 256, SDC_EINVAL,
-                "sdc_attn: bad shape (ntok=%d, max 256)", ntok);
+    SDC_REQUIRE(outer > 0 && inner > 0 && heads > 0 && ntok > 0, SDC_EINVAL, "sdc_attn: bad shape (ntok=%d)", ntok);
+    // past 256 tokens only the streaming kernel's domain is served; everything else is refused here, before any launch
+    SDC_REQUIRE(ntok <= 256 || (!rot && !bias && q_st == 1 && o_st == 1 && ntok <= sdc::ATTN_LONG_MAX), SDC_EINVAL,
+                "sdc_attn: bad shape (ntok=%d): more than 256 tokens need rot == bias == null, contiguous tokens (q_st == o_st == 1) "
+                "and ntok <= %d", ntok, sdc::ATTN_LONG_MAX);
     AttnArgs a;
     a.qkv = qkv; a.out = out; a.rot = rot; a.bias = bias;
     a.outer = outer; a.inner = inner; a.heads = heads; a.ntok = ntok;
@@ -608,6 +612,8 @@ extern "C" int sdc_attn(const float* qkv, float* out, const float* rot, const fl
         hipLaunchKernelGGL(attn256_kernel, dim3((unsigned)(outer * inner * heads)), dim3(NT), ldsb, sdc::as_stream(stream), a);
         return sdc::check_launch("sdc_attn[mfma 256]");
     }
+    if (ntok > 256)        // (keyed on ntok alone, never on the batch: csrc/sdc_attn_long.hip)
+        return sdc::attn_long(qkv, out, outer, inner, heads, ntok, q_so, q_sc, q_si, o_so, o_sc, o_si, stream);
     int nseq = NT / ntok;
     if (nseq < 1) nseq = 1;
     const int nseq_tot = outer * inner;

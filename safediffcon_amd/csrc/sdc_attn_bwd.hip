@@ -6,6 +6,7 @@
 // output, addressed through strides; the gradients are written in the same layout.  These are correctness-first fp32 VALU
 // kernels: the cores hold ~1 % of a U-Net's FLOPs, their projections run on the MFMA conv kernels.
 #include "sdc_common.h"
+#include "sdc_attn_long.h"
 
 namespace {
 
@@ -655,7 +656,7 @@ __global__ __launch_bounds__(NT) void la_bwd_fin_kernel(const LaBwdArgs a, const
 }  // namespace
 
 extern "C" size_t sdc_attn_bwd_bytes(int outer, int inner, int heads, int ntok) {
-    (void)outer; (void)inner;
+    if (ntok > 256) return sdc::attn_long_bwd_bytes(outer, inner, heads, ntok);     // row statistics: O(rows)
     return (size_t)1024 * heads * ntok * ntok * sizeof(float);
 }
 
@@ -663,7 +664,14 @@ extern "C" int sdc_attn_bwd(const float* qkv, const float* dout, const float* ro
                             void* work, int outer, int inner, int heads, int ntok, int64_t q_so, int64_t q_sc, int64_t q_si,
                             int64_t q_st, int64_t o_so, int64_t o_sc, int64_t o_si, int64_t o_st, void* stream) {
     SDC_REQUIRE(qkv && dout && dqkv, SDC_ENULL, "sdc_attn_bwd: null pointer");
-    SDC_REQUIRE(outer > 0 && inner > 0 && heads > 0 && ntok > 0 && ntok <= 256, SDC_EINVAL, "sdc_attn_bwd: bad shape (ntok=%d, max 256)", ntok);
+    SDC_REQUIRE(outer > 0 && inner > 0 && heads > 0 && ntok > 0, SDC_EINVAL, "sdc_attn_bwd: bad shape (ntok=%d)", ntok);
+    if (ntok > 256) {      // the streaming kernels' domain or nothing (csrc/sdc_attn_long.hip); refused before any launch
+        SDC_REQUIRE(!rot && !bias && !dbias && q_st == 1 && o_st == 1 && ntok <= sdc::ATTN_LONG_MAX, SDC_EINVAL,
+                    "sdc_attn_bwd: bad shape (ntok=%d): more than 256 tokens need rot == bias == dbias == null, contiguous tokens "
+                    "(q_st == o_st == 1) and ntok <= %d", ntok, sdc::ATTN_LONG_MAX);
+        SDC_REQUIRE(work, SDC_ENULL, "sdc_attn_bwd: more than 256 tokens need the sdc_attn_bwd_bytes(...) workspace");
+        return sdc::attn_long_bwd(qkv, dout, dqkv, work, outer, inner, heads, ntok, q_so, q_sc, q_si, o_so, o_sc, o_si, stream);
+    }
     SDC_REQUIRE(!bias || !dbias || (ntok <= 32 && work), SDC_EINVAL, "sdc_attn_bwd: the bias gradient is built for ntok <= 32 and needs the workspace");
     AttnBwdArgs a;
     a.qkv = qkv; a.dout = dout; a.rot = rot; a.bias = bias; a.dqkv = dqkv;

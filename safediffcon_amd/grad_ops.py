@@ -190,6 +190,7 @@ def attn_core_bwd(qkv, dout, heads, outer, inner, ntok, qs, os_, rot=None, bias=
     dbias = work = None
     if bias is not None:
         dbias = torch.empty_like(bias)
+    if bias is not None or ntok > 256:        # the bias-gradient partials / the streaming kernels' row statistics
         work = torch.empty(int(lib.sdc_attn_bwd_bytes(outer, inner, heads, ntok)) // 4, dtype=torch.float32, device=qkv.device)
     check(lib.sdc_attn_bwd(qkv.data_ptr(), dout.data_ptr(), 0 if rot is None else rot.data_ptr(), 0 if bias is None else bias.data_ptr(),
                            dqkv.data_ptr(), 0 if dbias is None else dbias.data_ptr(), 0 if work is None else work.data_ptr(),

@@ -34,7 +34,6 @@ namespace {
 inline int lab_slots(int ns) { const int s = 256 / ns; return s > 128 ? 128 : s; }
 constexpr float SCALE = 0.17677669529663687f;   // dim_head^-0.5
 #define MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f32_32x32x2f32(a_, b_, c_, 0, 0, 0)
-__device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }      // accumulator register -> row
 
 // the workspace: offsets in floats.  Every region but wt is [slot][...]; ns = pick_nsplit's (unclamped) split count
 struct LabWs {
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(NT) void lab_wt_kernel(const float* __restrict__ wq
     wt[(int64_t)threadIdx.x * C + blockIdx.x] = wqkv[(int64_t)blockIdx.x * (3 * HID) + threadIdx.x];
 }
 
-// channel norm of a tile as norm_tile (sdc_lablock.hip) has it: xs[c][tok] = xh * g; v becomes xh; returns the factor xh was scaled
+// channel norm of a tile as norm_tile_regs (sdc_lablock_tile.h) has it: xs[c][tok] = xh * g; v becomes xh; returns the factor xh was scaled
 // by: rstd (mode 0, LayerNorm: xh = (x - mean) rstd) or sqrt(C) / max(||x||, 1e-12) (mode 1, RMSNorm: xh = x f).  `live` is 0 where
 // mode 1's clamp holds (the backward then drops the term through the norm, as sdc_chan_norm_bwd does) and 1 everywhere else.
 template <int C>

@@ -53,12 +53,10 @@ struct La16Args {
     int64_t so, sc, si;
 };
 
-__host__ __device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
 // 2^d for an integer-valued d <= 0 (-inf included): exact
 __device__ __forceinline__ float pow2_neg(float d) { return ldexpf(1.0f, (int)fmaxf(d, -200.0f)); }
 
-// norm_tile of sdc_lablock.hip (the same fp32 expressions: xn before its rounding has la_blk's bits) storing xn as fp16:
+// norm_tile_regs (the fp32 expressions of every build: xn before its rounding has la_blk's bits) storing xn as fp16:
 // xt[tok][c] always; xc[c][pos(tok)], when given, with pos = tok with bits 2 and 3 swapped -- positions 16 q + 8 lh + j of a row hold
 // the tokens 16 q + row(j, lh) of the tile, the order in which a lane's accumulator registers walk the tokens.
 template <int C>
@@ -66,51 +64,8 @@ __device__ __forceinline__ void norm_tile16(float (&v)[C / 4], const float* __re
                                             _Float16* __restrict__ xc, float* __restrict__ xr, float* __restrict__ red, int tid) {
     constexpr int CG = C / 4, CP = cpitch(C);
     const int tok = tid & 63, grp = tid >> 6;
-    if (xr) {
-#pragma unroll
-        for (int k = 0; k < CG; ++k) xr[(grp * CG + k) * XP + tok] = v[k];
-    }
-    typedef float la_f2 __attribute__((ext_vector_type(2)));
-    la_f2 s2 = {0.f, 0.f};
     float o[CG];
-    if (mode == 0) {
-#pragma unroll
-        for (int k = 0; k < CG; k += 2) s2 += la_f2{v[k], v[k + 1]};
-        red[grp * TT + tok] = s2.x + s2.y;
-        __syncthreads();
-        const float mean = (red[tok] + red[TT + tok] + red[2 * TT + tok] + red[3 * TT + tok]) * (1.0f / C);
-        const la_f2 m2 = {mean, mean};
-        la_f2 q2 = {0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < CG; k += 2) {
-            const la_f2 d2 = la_f2{v[k], v[k + 1]} - m2;
-            v[k] = d2.x; v[k + 1] = d2.y;
-            q2 += d2 * d2;
-        }
-        red[(4 + grp) * TT + tok] = q2.x + q2.y;
-        __syncthreads();
-        const float var = (red[4 * TT + tok] + red[5 * TT + tok] + red[6 * TT + tok] + red[7 * TT + tok]) * (1.0f / C);
-        const float rstd = rsqrtf(var + eps);
-        const la_f2 r2 = {rstd, rstd};
-#pragma unroll
-        for (int k = 0; k < CG; k += 2) {
-            const la_f2 o2 = la_f2{v[k], v[k + 1]} * r2 * la_f2{g[grp * CG + k], g[grp * CG + k + 1]};
-            o[k] = o2.x; o[k + 1] = o2.y;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < CG; k += 2) { const la_f2 d2 = {v[k], v[k + 1]}; s2 += d2 * d2; }
-        red[grp * TT + tok] = s2.x + s2.y;
-        __syncthreads();
-        const float nrm = sqrtf(red[tok] + red[TT + tok] + red[2 * TT + tok] + red[3 * TT + tok]);
-        const float f = sqrtf((float)C) / fmaxf(nrm, 1e-12f);
-        const la_f2 f2 = {f, f};
-#pragma unroll
-        for (int k = 0; k < CG; k += 2) {
-            const la_f2 o2 = la_f2{v[k], v[k + 1]} * f2 * la_f2{g[grp * CG + k], g[grp * CG + k + 1]};
-            o[k] = o2.x; o[k + 1] = o2.y;
-        }
-    }
+    norm_tile_regs<C>(v, g, mode, eps, xr, red, tid, o);
     half8* xo = reinterpret_cast<half8*>(xt + tok * CP + grp * CG);
     const int pos = (tok & ~12) | ((tok & 4) << 1) | ((tok & 8) >> 1);
 #pragma unroll
@@ -165,19 +120,9 @@ __global__ __launch_bounds__(NT, (C == 64 ? 2 : 1)) void la16_ctx(const La16Args
     if (GN) __syncthreads();                        // coefficient table complete
     for (int tile = t0; tile < t1; ++tile) {
         if (GN) {
-            // h once, here, in fp32: pass 2 reads it back from the block's own output buffer (la_blk_ctx)
+            // h once, here, in fp32: pass 2 reads it back from the block's own output buffer
             gn_apply_tile<C>(xv, rseq ? rseq + (int64_t)tile * TT : nullptr, a.sc, gcoef, tid);
-            float* hb = a.gn_hout + o * a.so + i * a.si + (int64_t)tile * TT;
-            constexpr int CG = C / 4;
-            la_gptr hp = la_uni(hb + (int64_t)(__builtin_amdgcn_readfirstlane(tid >> 6) * CG) * a.sc);
-            uint32_t hoff = (uint32_t)(tid & 63) * 4u;
-#pragma unroll
-            for (int k = 0; k < CG; ++k) {
-                asm volatile("" : "+v"(hoff));
-                la_st(hp, hoff, xv[k]);
-                hp += a.sc;
-                asm volatile("" : "+s"(hp));
-            }
+            gn_store_h<C>(a.gn_hout + o * a.so + i * a.si + (int64_t)tile * TT, a.sc, tid, xv);
         }
         norm_tile16<C>(xv, a.g_pre, a.pre_mode, a.eps, xt, xc, nullptr, red, tid);
         if (tile + 1 < t1) fetch_tile<C>(xseq + (int64_t)(tile + 1) * TT, a.sc, tid, xv);
@@ -191,7 +136,8 @@ __global__ __launch_bounds__(NT, (C == 64 ? 2 : 1)) void la16_ctx(const La16Args
             kacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, wk[s], kacc[0], 0, 0, 0);
             kacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, wk[s], kacc[1], 0, 0, 0);
         }
-        // online softmax over tokens, per d, against an integer exponent
+        // online softmax over tokens, per d, against an integer exponent: not la_softmax_tok -- the reference is ceil(m log2e), the
+        // factor pow2_neg's exact power of two, and the first maximum has a form of its own
         // (the first maximum in plain C++, as in la16_out: it reads the accumulators the last two MFMAs have just written, and
         // behind la_max3's asm statement the compiler places no wait states -- at C = 64 the v_max3_f32 stood directly behind
         // the MFMA and read a register that was stale or not with the load of the CU: run-to-run differences in the last bits
@@ -212,12 +158,7 @@ __global__ __launch_bounds__(NT, (C == 64 ? 2 : 1)) void la16_ctx(const La16Args
             ps += kacc[0][r] + kacc[1][r];
         }
         psum = psum * f + ps;
-        if (__builtin_amdgcn_ballot_w64(f != 1.0f)) {           // (wave-uniform: a multiplication by 1 is skipped)
-#pragma unroll
-            for (int t = 0; t < NCT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) macc[t][r] *= f;
-        }
+        la_rescale<NCT>(macc, f);
         // step (j, q): tokens j*32 + row(8 q + jj, lh) = positions j*32 + 16 q + 8 lh + jj of the channel-major rows
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -232,14 +173,8 @@ __global__ __launch_bounds__(NT, (C == 64 ? 2 : 1)) void la16_ctx(const La16Args
             }
         __syncthreads();                             // xt / xc are rewritten by the next tile
     }
-    // partial result of this split: M[32][C], e[32] (the integer exponent), s[32]
-    float* pp = a.part + (((int64_t)seq * a.nsplit + split) * 4 + head) * (32 * (C + 2));
-#pragma unroll
-    for (int t = 0; t < NCT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) pp[l31 * C + t * 32 + crow(r, lh)] = macc[t][r];
-    const float stot = psum + __shfl_xor(psum, 32, 64);
-    if (lh == 0) { pp[32 * C + l31] = erun; pp[32 * C + 32 + l31] = stot; }
+    // the partial's m is e, the integer exponent
+    la_store_partial<C>(a.part + (((int64_t)seq * a.nsplit + split) * 4 + head) * (32 * (C + 2)), macc, erun, psum, l31, lh);
 }
 
 // ------------------------------------------------------------------ mid: per (sequence, head)
@@ -346,24 +281,7 @@ __global__ __launch_bounds__(NT, (C == 64 ? 2 : 1)) SDC_NO_DS_MERGE void la16_ou
         // softmax over d (the 32 rows of the head) per token, times dim_head^-0.5: fp32; then one rounding
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            float m = fmaxf(qacc[j][0], qacc[j][1]);
-#pragma unroll
-            for (int r = 2; r < 16; r += 2) m = la_max3(m, qacc[j][r], qacc[j][r + 1]);
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            typedef float la_f2 __attribute__((ext_vector_type(2)));
-            const float nml = -m * LOG2E;
-            const la_f2 l2 = {LOG2E, LOG2E}, n2 = {nml, nml};
-            la_f2 s2 = {0.f, 0.f};
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const la_f2 e2 = la_f2{qacc[j][r], qacc[j][r + 1]} * l2 + n2;
-                const la_f2 p2 = {__builtin_amdgcn_exp2f(e2.x), __builtin_amdgcn_exp2f(e2.y)};
-                qacc[j][r] = p2.x; qacc[j][r + 1] = p2.y;
-                s2 += p2;
-            }
-            float s = s2.x + s2.y;
-            s += __shfl_xor(s, 32, 64);
-            const float f = 0.17677669529663687f * __builtin_amdgcn_rcpf(s);
+            const float f = la_softmax_d<la_max3>(qacc[j]);
             // registers 8 q .. 8 q + 7: the K fragment of step 2 wave + q for column tile j, on the lane that reads it back
 #pragma unroll
             for (int q = 0; q < 2; ++q) qs[((2 * wave + q) * 2 + j) * 64 + lane] = frag(qacc[j], 8 * q, f);
@@ -380,74 +298,8 @@ __global__ __launch_bounds__(NT, (C == 64 ? 2 : 1)) SDC_NO_DS_MERGE void la16_ou
 #pragma unroll
             for (int u = 0; u < TPW; ++u)
                 yacc[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tf[s], qs[(s * 2 + ct0 + u) * 64 + lane], yacc[u], 0, 0, 0);
-        // channel norm over the C rows of each token column (la_blk_out's)
-        if (a.post_mode >= 0) {
-            float st[TPW];
-#pragma unroll
-            for (int u = 0; u < TPW; ++u) {
-                float s = 0.f;
-                if (a.post_mode == 0) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s += yacc[u][r];
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s += yacc[u][r] * yacc[u][r];
-                }
-                s += __shfl_xor(s, 32, 64);
-                if (lh == 0) red[rt * TT + (ct0 + u) * 32 + l31] = s;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < TPW; ++u) {
-                float s = 0.f;
-#pragma unroll
-                for (int q = 0; q < NRT; ++q) s += red[q * TT + (ct0 + u) * 32 + l31];
-                st[u] = s;
-            }
-            if (a.post_mode == 0) {
-#pragma unroll
-                for (int u = 0; u < TPW; ++u) {
-                    const float mean = st[u] * (1.0f / C);
-                    float q = 0.f;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { yacc[u][r] -= mean; q += yacc[u][r] * yacc[u][r]; }
-                    q += __shfl_xor(q, 32, 64);
-                    if (lh == 0) red[(4 + rt) * TT + (ct0 + u) * 32 + l31] = q;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int u = 0; u < TPW; ++u) {
-                    float q = 0.f;
-#pragma unroll
-                    for (int w = 0; w < NRT; ++w) q += red[(4 + w) * TT + (ct0 + u) * 32 + l31];
-                    const float rstd = rsqrtf(q * (1.0f / C) + a.eps);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) yacc[u][r] = yacc[u][r] * rstd * bg[C + rt * 32 + crow(r, lh)];
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < TPW; ++u) {
-                    const float f = sqrtf((float)C) / fmaxf(sqrtf(st[u]), 1e-12f);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) yacc[u][r] = yacc[u][r] * f * bg[C + rt * 32 + crow(r, lh)];
-                }
-            }
-        }
-        // + x, store (tokens on lanes: coalesced rows; scalar row base + one lane offset, host check `4 sc` elements < 2^30)
-#pragma unroll
-        for (int u = 0; u < TPW; ++u) {
-            const int col = (ct0 + u) * 32 + l31;
-            uint32_t loff = (uint32_t)((int64_t)(4 * lh) * a.sc + col) * 4u;
-            la_gptr yrow = la_uni(yseq + (int64_t)(rt * 32) * a.sc + (int64_t)tile * TT);
-            const float* xrow = xr + (rt * 32 + 4 * lh) * XP + col;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                asm volatile("" : "+v"(loff));
-                la_st(yrow, loff, yacc[u][r] + xrow[((r & 3) + 8 * (r >> 2)) * XP]);
-                yrow += ((r & 3) == 3 ? 5 : 1) * a.sc;
-                asm volatile("" : "+s"(yrow));
-            }
-        }
+        if (a.post_mode >= 0) la_post_norm<C, false>(yacc, a.post_mode, a.eps, bg, red, rt, ct0, l31, lh);
+        la_store_residual<C>(yacc, yseq + (int64_t)tile * TT, a.sc, xr, rt, ct0, l31, lh);
         __syncthreads();                             // xt / qs / red / xr are rewritten by the next tile
     }
 }
@@ -469,33 +321,18 @@ int linattn_block_f16_impl(const char* who, const float* x, const float* gn_stat
                            const float* g_post, void* work, float* y, int outer, int inner, int C, int64_t n, int64_t so, int64_t sc,
                            int64_t si, int pre_mode, int post_mode, float eps, void* stream) {
     SDC_REQUIRE(x && g_pre && wqkv && wo && wpk && work && y, SDC_ENULL, "%s: null pointer", who);
-    SDC_REQUIRE(C == 64 || C == 128, SDC_EINVAL, "%s: dim must be 64 or 128 (got %d)", who, C);
-    SDC_REQUIRE(outer > 0 && inner > 0 && n > 0 && n % TT == 0, SDC_EINVAL, "%s: tokens must be a multiple of 64", who);
-    SDC_REQUIRE((pre_mode == 0 || pre_mode == 1) && post_mode >= -1 && post_mode <= 1, SDC_EINVAL, "%s: bad norm mode", who);
-    SDC_REQUIRE(post_mode < 0 || g_post, SDC_ENULL, "%s: post norm needs its gain", who);
-    const int64_t nseq = (int64_t)outer * inner;
-    SDC_REQUIRE(nseq < 65536, SDC_EINVAL, "%s: outer*inner must be < 65536", who);
-    SDC_REQUIRE(sc > 0 && sc < (1ll << 27), SDC_EINVAL, "%s: channel stride must stay below 2^27 elements (32-bit lane offsets)", who);
+    La16Args a;
+    LaGrids g;
+    float* tt_at;
+    const int rc0 = la_host_setup(who, a, x, gn_stats, gn_gamma, gn_beta, gn_G, gn_res, g_pre, bo, g_post, work, y, outer, inner, C, n, so, sc,
+                                  si, pre_mode, post_mode, eps, g, &tt_at);
+    if (rc0 != SDC_OK) return rc0;
     // the kernels read the fragments of the weights and of T (behind the partials in `work`) with 16-byte vector loads
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(wpk) % 16 == 0, SDC_EALIGN, "%s: the fp16 weight buffer must be 16-byte aligned", who);
     SDC_REQUIRE(reinterpret_cast<uintptr_t>(work) % 16 == 0, SDC_EALIGN, "%s: work must be 16-byte aligned", who);
-    La16Args a;
-    a.x = x; a.g_pre = g_pre; a.wpk = reinterpret_cast<const _Float16*>(wpk); a.wqkv = wqkv; a.wo = wo; a.bo = bo; a.g_post = g_post; a.y = y;
-    a.gn_stats = gn_stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.gn_res = gn_res; a.gn_G = gn_G; a.gn_hout = nullptr;
-    a.inner = inner; a.ntiles = (int)(n / TT);
-    const int ns0 = pick_nsplit(nseq, a.ntiles);
-    a.tiles_per_split = (a.ntiles + ns0 - 1) / ns0;
-    a.nsplit = (a.ntiles + a.tiles_per_split - 1) / a.tiles_per_split;     // no empty splits
-    // the layout sdc_linattn_block_f16_bytes promised: fp32 partials (sized for the unclamped split count; a multiple of 16 bytes), then T
-    a.part = reinterpret_cast<float*>(work);
-    a.tt = reinterpret_cast<_Float16*>(a.part + nseq * ns0 * 4 * 32 * (C + 2));
-    int tpb = (int)((nseq * a.ntiles + 1023) / 1024);
-    a.tiles_per_blk = tpb < 1 ? 1 : (tpb > 8 ? 8 : tpb);
-    a.pre_mode = pre_mode; a.post_mode = post_mode; a.eps = eps;
-    a.so = so; a.sc = sc; a.si = si;
+    a.wpk = reinterpret_cast<const _Float16*>(wpk); a.wqkv = wqkv; a.wo = wo;
+    a.tt = reinterpret_cast<_Float16*>(tt_at);
     hipStream_t s = sdc::as_stream(stream);
-    const dim3 g1((unsigned)a.nsplit, (unsigned)nseq), gm(4, (unsigned)nseq),
-        g2((unsigned)((a.ntiles + a.tiles_per_blk - 1) / a.tiles_per_blk), (unsigned)nseq);
     const size_t l1 = lds_ctx(C), l2 = lds_out(C);
     static std::atomic<uint64_t> attr{0};
     SDC_LDS_OPTIN(attr, la16_out<128>, 96 * 1024, who);          // 70 KB; every other instantiation stays below 64 KB
@@ -503,15 +340,15 @@ int linattn_block_f16_impl(const char* who, const float* x, const float* gn_stat
     La16Args a2 = a;                                // pass 2 of the GroupNorm-on-load form: x = the h pass 1 left in y
     if (gn) { a.gn_hout = y; a2.x = y; a2.gn_stats = nullptr; }
     if (C == 64) {
-        if (gn) hipLaunchKernelGGL((la16_ctx<64, true>), g1, dim3(NT), l1, s, a);
-        else hipLaunchKernelGGL((la16_ctx<64, false>), g1, dim3(NT), l1, s, a);
-        hipLaunchKernelGGL(la16_mid<64>, gm, dim3(NT), 0, s, a);
-        hipLaunchKernelGGL(la16_out<64>, g2, dim3(NT), l2, s, a2);
+        if (gn) hipLaunchKernelGGL((la16_ctx<64, true>), g.ctx, dim3(NT), l1, s, a);
+        else hipLaunchKernelGGL((la16_ctx<64, false>), g.ctx, dim3(NT), l1, s, a);
+        hipLaunchKernelGGL(la16_mid<64>, g.mid, dim3(NT), 0, s, a);
+        hipLaunchKernelGGL(la16_out<64>, g.out, dim3(NT), l2, s, a2);
     } else {
-        if (gn) hipLaunchKernelGGL((la16_ctx<128, true>), g1, dim3(NT), l1, s, a);
-        else hipLaunchKernelGGL((la16_ctx<128, false>), g1, dim3(NT), l1, s, a);
-        hipLaunchKernelGGL(la16_mid<128>, gm, dim3(NT), 0, s, a);
-        hipLaunchKernelGGL(la16_out<128>, g2, dim3(NT), l2, s, a2);
+        if (gn) hipLaunchKernelGGL((la16_ctx<128, true>), g.ctx, dim3(NT), l1, s, a);
+        else hipLaunchKernelGGL((la16_ctx<128, false>), g.ctx, dim3(NT), l1, s, a);
+        hipLaunchKernelGGL(la16_mid<128>, g.mid, dim3(NT), 0, s, a);
+        hipLaunchKernelGGL(la16_out<128>, g.out, dim3(NT), l2, s, a2);
     }
     return sdc::check_launch(who);
 }
@@ -534,8 +371,7 @@ extern "C" int sdc_linattn_block_f16_ok(int C, int64_t n) { return (C == 64 || C
 extern "C" size_t sdc_linattn_block_f16_bytes(int outer, int inner, int C, int64_t n) {
     if (outer <= 0 || inner <= 0 || n <= 0 || (C != 64 && C != 128)) return 0;
     const int64_t nseq = (int64_t)outer * inner;
-    const int ns = pick_nsplit(nseq, (int)(n / TT));
-    return sizeof(float) * (size_t)(nseq * ns * 4 * 32 * (C + 2)) + sizeof(_Float16) * (size_t)(nseq * HID * C);
+    return sizeof(float) * la_part_floats(nseq, C, n) + sizeof(_Float16) * (size_t)(nseq * HID * C);
 }
 
 extern "C" int sdc_linattn_block_f16(const float* x, const float* g_pre, const float* wqkv, const float* wo, const void* wpk, const float* bo,

@@ -365,11 +365,22 @@ int sdc_tattn_block_x3_impl(int C, int ntok, int inner);
  * (csrc/sdc_attn_long.hip) -- rot and bias null, tokens contiguous in qkv and out (q_st == o_st == 1).  Its address
  * arithmetic is 64-bit; the 32-bit quantities are the token index and the grid outer*inner*heads*ceil(ntok/128) (checked
  * per call), so the cap is not an arithmetic limit: 4096 is the largest size held against the fp64 reference.  Anything
- * else past 256 tokens is SDC_EINVAL before any launch.  The kernel is chosen by ntok and the strides alone, never by
- * outer or inner. */
+ * else past 256 tokens is SDC_EINVAL before any launch.  The kernel is chosen by sdc_attn_route below: by ntok, the strides
+ * and the per-sample inner alone, never by outer.  Temporal attention (frame-strided tokens, q_si == o_si == 1) runs on the
+ * matrix cores at 32 frames (inner % 8 == 0) and at 64, 96 and 128 frames (any inner >= 1; csrc/sdc_tattn_frames.hip). */
 int sdc_attn(const float* qkv, float* out, const float* rot, const float* bias, int outer, int inner, int heads,
              int ntok, int64_t q_so, int64_t q_sc, int64_t q_si, int64_t q_st,
              int64_t o_so, int64_t o_sc, int64_t o_si, int64_t o_st, void* stream);
+
+/* The routing predicate sdc_attn (backward == 0) and sdc_attn_bwd (backward != 0) both dispatch through: host arithmetic on the
+ * shape and the strides, no device, no pointer, independent of outer and heads.  has_rot / has_bias: rot / bias non-null;
+ * want_dbias: dbias non-null (backward only).  Returns 0 generic kernel, 1 32-frame MFMA, 2 256-token MFMA, 3 streaming
+ * (ntok > 256), 4 the 64 / 96 / 128-frame MFMA kernels (frame-strided tokens q_st != 1, q_si == o_si == 1, frame stride x ntok x 4
+ * bytes < 2^32 in qkv and out), or SDC_EINVAL with the entry point's own message for a call the entry point refuses.
+ * Route 2 is reported for every shape in the 256-token kernel's domain; sdc_attn falls back to route 0 at run time where qkv
+ * or its strides are not 16-byte aligned, which is no property of the shape.  The backward has no route 2. */
+int sdc_attn_route(int inner, int ntok, int64_t q_si, int64_t q_st, int64_t o_si, int64_t o_st, int has_rot, int has_bias,
+                   int want_dbias, int backward);
 
 /* ------------------------------------------------------------ elementwise */
 /* kind 0: SiLU, 1: exact (erf) GELU -- time_mlp / ResnetBlock.mlp (unet.py:152-155,310-315) */
@@ -716,8 +727,12 @@ int sdc_pack_batch_run(const SdcPackItem* items_dev, int n, int total_blocks, in
 
 /* Backward of the attention cores (same tensor conventions as sdc_attn / sdc_linattn: q, k, v = channel ranges of qkv, the
  * gradients dqkv in the same layout; dout = dL/dout in the layout of `out`).
- * sdc_attn_bwd: dbias (heads, ntok, ntok) = sum over sequences of dS, or null (built for ntok <= 32: the temporal attention's
- * relative-position bias, conv3d.py:74-112); work = sdc_attn_bwd_bytes(...) bytes when dbias is requested.
+ * sdc_attn_bwd: dbias (heads, ntok, ntok) = sum over sequences of dS, or null.  The bias gradient is built for ntok <= 32 and for
+ * route 4 of sdc_attn_route (64, 96 or 128 frames with contiguous pixels): the temporal attention's relative-position bias,
+ * conv3d.py:74-112; anywhere else a non-null dbias is SDC_EINVAL before any launch.  work = sdc_attn_bwd_bytes(...) bytes when
+ * dbias is requested, and only then: it holds one partial table per workgroup slot, summed in a fixed order (no atomics).
+ * sdc_attn_bwd_bytes: 1024 slots x heads x ntok^2 floats, except at ntok 64 / 96 / 128: 256 slots (67 MB instead of 268 MB at
+ * 128 frames and 4 heads).
  * 256 < ntok <= 4096 (the domain of sdc_attn above, dbias null): work is REQUIRED -- two floats per (sequence, head, token),
  * the row statistics the gradient recomputes the probabilities from; nothing ntok x ntok is stored, no atomics. */
 size_t sdc_attn_bwd_bytes(int outer, int inner, int heads, int ntok);

@@ -128,6 +128,7 @@ SIGNATURES = {
     "sdc_tattn_block_x3_impl": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "sdc_attn": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _i64, _i64, _i64,
                            _i64, _i64, _i64, _i64, _stream]),
+    "sdc_attn_route": (C.c_int, [C.c_int, C.c_int, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdc_act": (C.c_int, [_f32p, _f32p, _i64, C.c_int, _stream]),
     "sdc_guide_reduce": (C.c_int, [C.POINTER(SdcStepDesc), _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, _stream]),
     "sdc_step_update": (C.c_int, [C.POINTER(SdcStepDesc), _f32p, _f32p, _f32p, _f32p, _i32p, _i32p, _f32p, _i64,

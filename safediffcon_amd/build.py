@@ -6,8 +6,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsdc_hip.so")
-SOURCES = ["sdc_api.hip", "sdc_conv.hip", "sdc_conv_wino.hip", "sdc_conv_f16.hip", "sdc_conv_stem_f16.hip", "sdc_conv_stem_x3.hip", "sdc_conv_gemm_x3.hip", "sdc_conv_pw_x3.hip", "sdc_conv_wino_x3.hip", "sdc_norm.hip", "sdc_attn.hip", "sdc_attn_long.hip", "sdc_lablock.hip", "sdc_lablock_f16.hip", "sdc_lablock_x3.hip", "sdc_lablock_bwd.hip", "sdc_tablock.hip", "sdc_tablock_f16.hip", "sdc_tablock_x3.hip", "sdc_tablock_bwd.hip", "sdc_step.hip", "sdc_solver.hip", "sdc_burgers_gen.hip", "sdc_grad.hip", "sdc_wgrad_f16.hip", "sdc_attn_bwd.hip", "sdc_kstar.hip", "sdc_smoke.hip", "sdc_linear.hip", "sdc_optim.hip"]
-HEADERS = ["sdc_common.h", "sdc_attn_long.h", "sdc_lablock_tile.h", "sdc_lablock_pass.h", "sdc_tablock_tile.h", "sdc_conv_stem_tile.h", "sdc_split3.h", "sdc_f16frag.h", "sdc_conv.h", "sdc_conv_wino3s.inc", "sdc_conv_wino2s.inc", "sdc_conv_pw2.inc"]      # csrc files the translation units include
+SOURCES = ["sdc_api.hip", "sdc_conv.hip", "sdc_conv_wino.hip", "sdc_conv_f16.hip", "sdc_conv_stem_f16.hip", "sdc_conv_stem_x3.hip", "sdc_conv_gemm_x3.hip", "sdc_conv_pw_x3.hip", "sdc_conv_wino_x3.hip", "sdc_norm.hip", "sdc_attn.hip", "sdc_attn_long.hip", "sdc_tattn_frames.hip", "sdc_lablock.hip", "sdc_lablock_f16.hip", "sdc_lablock_x3.hip", "sdc_lablock_bwd.hip", "sdc_tablock.hip", "sdc_tablock_f16.hip", "sdc_tablock_x3.hip", "sdc_tablock_bwd.hip", "sdc_step.hip", "sdc_solver.hip", "sdc_burgers_gen.hip", "sdc_grad.hip", "sdc_wgrad_f16.hip", "sdc_attn_bwd.hip", "sdc_kstar.hip", "sdc_smoke.hip", "sdc_linear.hip", "sdc_optim.hip"]
+HEADERS = ["sdc_common.h", "sdc_attn_long.h", "sdc_tattn_frames.h", "sdc_lablock_tile.h", "sdc_lablock_pass.h", "sdc_tablock_tile.h", "sdc_conv_stem_tile.h", "sdc_split3.h", "sdc_f16frag.h", "sdc_conv.h", "sdc_conv_wino3s.inc", "sdc_conv_wino2s.inc", "sdc_conv_pw2.inc"]      # csrc files the translation units include
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

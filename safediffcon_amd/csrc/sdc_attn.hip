@@ -5,6 +5,7 @@
 // rearrange copy is ever materialised ('b (h c) x y -> b h c (x y)', 'b c f h w -> b (h w) f c').
 #include "sdc_common.h"
 #include "sdc_attn_long.h"
+#include "sdc_tattn_frames.h"
 
 namespace {
 
@@ -574,17 +575,19 @@ extern "C" int sdc_attn(const float* qkv, float* out, const float* rot, const fl
                         int64_t o_sc, int64_t o_si, int64_t o_st, void* stream) {
     SDC_REQUIRE(qkv && out, SDC_ENULL, "sdc_attn: null pointer");
     SDC_REQUIRE(outer > 0 && inner > 0 && heads > 0 && ntok > 0, SDC_EINVAL, "sdc_attn: bad shape (ntok=%d)", ntok);
-    // past 256 tokens only the streaming kernel's domain is served; everything else is refused here, before any launch
-    SDC_REQUIRE(ntok <= 256 || (!rot && !bias && q_st == 1 && o_st == 1 && ntok <= sdc::ATTN_LONG_MAX), SDC_EINVAL,
-                "sdc_attn: bad shape (ntok=%d): more than 256 tokens need rot == bias == null, contiguous tokens (q_st == o_st == 1) "
-                "and ntok <= %d", ntok, sdc::ATTN_LONG_MAX);
+    // one predicate decides the kernel, for this entry point and for sdc_attn_bwd (csrc/sdc_tattn_frames.hip); past 256 tokens only the
+    // streaming kernel's domain is served: everything else is refused there, before any launch
+    const int route = sdc_attn_route(inner, ntok, q_si, q_st, o_si, o_st, rot != nullptr, bias != nullptr, 0, 0);
+    if (route < 0) return route;
+    if (route == 4)        // 64 / 96 / 128 frames on the matrix cores
+        return sdc::tattn_frames(qkv, out, rot, bias, outer, inner, heads, ntok, q_so, q_sc, q_st, o_so, o_sc, o_st, stream);
     AttnArgs a;
     a.qkv = qkv; a.out = out; a.rot = rot; a.bias = bias;
     a.outer = outer; a.inner = inner; a.heads = heads; a.ntok = ntok;
     a.so = q_so; a.sc = q_sc; a.si = q_si; a.st = q_st;
     a.oso = o_so; a.osc = o_sc; a.osi = o_si; a.ost = o_st;
     a.tok_contig = (q_st == 1);
-    if (!a.tok_contig && ntok == 32 && inner % TA_NS == 0 && q_si == 1 && o_si == 1 && q_st > 0 && o_st > 0 && q_st < (1ll << 24) && o_st < (1ll << 24)) {     // (frame stride x 32 frames x 4 bytes < 2^32: 32-bit lane offsets)
+    if (route == 1) {     // (frame stride x 32 frames x 4 bytes < 2^32: 32-bit lane offsets)
         const int ns = inner % 16 == 0 ? 16 : 8;
         const int nblk = (outer * inner / ns) * heads;
         // tiles per workgroup: the largest of 4 / 2 / 1 that leaves a grid of a multiple of 8 heads (one head per workgroup under
@@ -604,7 +607,7 @@ extern "C" int sdc_attn(const float* qkv, float* out, const float* rot, const fl
         }
         return sdc::check_launch("sdc_attn[mfma]");
     }
-    if (a.tok_contig && ntok == 256 && !rot && !bias && o_st == 1 && q_sc % 4 == 0 && q_so % 4 == 0 && q_si % 4 == 0 &&
+    if (route == 2 && q_sc % 4 == 0 && q_so % 4 == 0 && q_si % 4 == 0 &&
         reinterpret_cast<uintptr_t>(qkv) % 16 == 0) {
         const size_t ldsb = sizeof(float) * (size_t)(32 * 256 + 32 * A2_VP);
         static std::atomic<uint64_t> attr2{0};
@@ -612,7 +615,7 @@ extern "C" int sdc_attn(const float* qkv, float* out, const float* rot, const fl
         hipLaunchKernelGGL(attn256_kernel, dim3((unsigned)(outer * inner * heads)), dim3(NT), ldsb, sdc::as_stream(stream), a);
         return sdc::check_launch("sdc_attn[mfma 256]");
     }
-    if (ntok > 256)        // (keyed on ntok alone, never on the batch: csrc/sdc_attn_long.hip)
+    if (route == 3)        // (keyed on ntok alone, never on the batch: csrc/sdc_attn_long.hip)
         return sdc::attn_long(qkv, out, outer, inner, heads, ntok, q_so, q_sc, q_si, o_so, o_sc, o_si, stream);
     int nseq = NT / ntok;
     if (nseq < 1) nseq = 1;

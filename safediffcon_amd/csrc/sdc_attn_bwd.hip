@@ -7,6 +7,7 @@
 // kernels: the cores hold ~1 % of a U-Net's FLOPs, their projections run on the MFMA conv kernels.
 #include "sdc_common.h"
 #include "sdc_attn_long.h"
+#include "sdc_tattn_frames.h"
 
 namespace {
 
@@ -657,6 +658,7 @@ __global__ __launch_bounds__(NT) void la_bwd_fin_kernel(const LaBwdArgs a, const
 
 extern "C" size_t sdc_attn_bwd_bytes(int outer, int inner, int heads, int ntok) {
     if (ntok > 256) return sdc::attn_long_bwd_bytes(outer, inner, heads, ntok);     // row statistics: O(rows)
+    if (sdc::tattn_frames_ntok(ntok)) return sdc::tattn_frames_bwd_bytes(heads, ntok);      // a bias gradient at these ntok is the frames kernel's
     return (size_t)1024 * heads * ntok * ntok * sizeof(float);
 }
 
@@ -665,14 +667,27 @@ extern "C" int sdc_attn_bwd(const float* qkv, const float* dout, const float* ro
                             int64_t q_st, int64_t o_so, int64_t o_sc, int64_t o_si, int64_t o_st, void* stream) {
     SDC_REQUIRE(qkv && dout && dqkv, SDC_ENULL, "sdc_attn_bwd: null pointer");
     SDC_REQUIRE(outer > 0 && inner > 0 && heads > 0 && ntok > 0, SDC_EINVAL, "sdc_attn_bwd: bad shape (ntok=%d)", ntok);
-    if (ntok > 256) {      // the streaming kernels' domain or nothing (csrc/sdc_attn_long.hip); refused before any launch
-        SDC_REQUIRE(!rot && !bias && !dbias && q_st == 1 && o_st == 1 && ntok <= sdc::ATTN_LONG_MAX, SDC_EINVAL,
-                    "sdc_attn_bwd: bad shape (ntok=%d): more than 256 tokens need rot == bias == dbias == null, contiguous tokens "
-                    "(q_st == o_st == 1) and ntok <= %d", ntok, sdc::ATTN_LONG_MAX);
+    // the same predicate as sdc_attn's (csrc/sdc_tattn_frames.hip); what it refuses is refused before any launch
+    const int route = sdc_attn_route(inner, ntok, q_si, q_st, o_si, o_st, rot != nullptr, bias != nullptr, dbias != nullptr, 1);
+    if (route < 0) return route;
+    if (route == 3) {      // the streaming kernels (csrc/sdc_attn_long.hip)
         SDC_REQUIRE(work, SDC_ENULL, "sdc_attn_bwd: more than 256 tokens need the sdc_attn_bwd_bytes(...) workspace");
         return sdc::attn_long_bwd(qkv, dout, dqkv, work, outer, inner, heads, ntok, q_so, q_sc, q_si, o_so, o_sc, o_si, stream);
     }
-    SDC_REQUIRE(!bias || !dbias || (ntok <= 32 && work), SDC_EINVAL, "sdc_attn_bwd: the bias gradient is built for ntok <= 32 and needs the workspace");
+    SDC_REQUIRE(!bias || !dbias || work, SDC_EINVAL,
+                "sdc_attn_bwd: the bias gradient is built for ntok <= 32, or 64, 96 or 128 frames with contiguous pixels, and needs the workspace");
+    if (route == 4) {      // 64 / 96 / 128 frames on the matrix cores; the partial tables are summed in sum_rows_kernel's fixed order
+        float* part = (bias && dbias) ? static_cast<float*>(work) : nullptr;
+        int nslots = 0;
+        const int rc = sdc::tattn_frames_bwd(qkv, dout, rot, bias, dqkv, part, &nslots, outer, inner, heads, ntok, q_so, q_sc, q_st, o_so,
+                                             o_sc, o_st, stream);
+        if (rc != SDC_OK) return rc;
+        if (part) {
+            const int nb = heads * ntok * ntok;
+            hipLaunchKernelGGL(sum_rows_kernel, dim3((nb + 63) / 64), dim3(64 * SR_G), 0, sdc::as_stream(stream), part, dbias, nb, nslots);
+        }
+        return sdc::check_launch("sdc_attn_bwd[frames]");
+    }
     AttnBwdArgs a;
     a.qkv = qkv; a.dout = dout; a.rot = rot; a.bias = bias; a.dqkv = dqkv;
     a.dbias_part = (bias && dbias) ? static_cast<float*>(work) : nullptr;
@@ -681,7 +696,7 @@ extern "C" int sdc_attn_bwd(const float* qkv, const float* dout, const float* ro
     a.oso = o_so; a.osc = o_sc; a.osi = o_si; a.ost = o_st;
     a.tok_contig = (q_st == 1);
     hipStream_t s = sdc::as_stream(stream);
-    if (!a.tok_contig && ntok == 32 && inner % TB_NS == 0 && q_si == 1 && o_si == 1) {
+    if (route == 1) {
         // temporal attention of the smoke net: the MFMA kernel
         a.nseq = TB_NS; a.ls = a.ld = a.lj = 0;
         a.ngrp = outer * inner / TB_NS;
